@@ -11,6 +11,12 @@ Launch (driver contract):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, prefills, warms up, times the K steps and prints one
+JSON result line. `--dump-outputs DIR` also writes the last timed step's
+outputs (greedy tokens + the logits behind them) as DIR/<name>.npy so two
+builds can be compared output for output; the inputs are seeded, identical
+from run to run. `--full` is where secondary measurements belong (none yet).
+
 One "step" advances every in-flight micro-batch by one token; value =
 whole-job decode tokens/sec = global_batch * steps / elapsed (max over ranks).
 Scaling is weak: micro-batch count = N pipeline stages with fixed per-mb
@@ -47,6 +53,37 @@ if _tuned.exists() and os.getenv("XOT_TUNABLEOP", "1") == "1":
 import torch  # noqa: E402
 
 
+DUMP_LOGIT_BYTES = 48 << 20  # logits sample budget; the whole dump stays under 64 MB
+
+
+def dump_outputs(ring, out_dir):
+  """Write what the last timed decode step produced on the last stage:
+  tokens.npy [M, B] (the greedy tokens the ring hands back), logits.npy
+  [M, B, C] (the logits they were picked from, at C vocabulary columns) and
+  logits_columns.npy [C] (which columns: all of them when they fit the
+  budget, else a fixed seeded sample). All float32/float64."""
+  import numpy as np
+  out = Path(out_dir)
+  out.mkdir(parents=True, exist_ok=True)
+  if any(l is None for l in ring.last_logits):
+    print(f"[bench] --dump-outputs: no decode step ran (--steps 0 --warmup 0), "
+          f"nothing written to {out}", file=sys.stderr)
+    return
+  if ring.device == "cuda":
+    torch.cuda.synchronize()
+  toks = torch.stack([t.reshape(-1) for t in ring.last_tokens()]).cpu().numpy()
+  np.save(out / "tokens.npy", toks.astype(np.float32))
+  rows = sum(l.shape[0] for l in ring.last_logits)
+  vocab = ring.last_logits[0].shape[-1]
+  n_cols = max(1, min(vocab, DUMP_LOGIT_BYTES // (4 * rows)))
+  cols = np.sort(np.random.default_rng(0).choice(vocab, n_cols, replace=False))
+  idx = torch.from_numpy(cols).to(ring.last_logits[0].device)
+  logits = torch.stack([l.reshape(l.shape[0], vocab).index_select(1, idx).float()
+                        for l in ring.last_logits]).cpu().numpy()
+  np.save(out / "logits.npy", logits)
+  np.save(out / "logits_columns.npy", cols.astype(np.float64))
+
+
 def main():
   p = argparse.ArgumentParser()
   p.add_argument("--gpus", type=int, default=1)
@@ -58,7 +95,13 @@ def main():
   p.add_argument("--no-graphs", action="store_true")
   p.add_argument("--device", type=str, default=None)
   p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
+  p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                 help="after the timed steps, write the last step's outputs to DIR/<name>.npy")
+  p.add_argument("--full", action="store_true",
+                 help="also run the secondary measurements (none today: a plain run "
+                      "already does only what the headline figure needs)")
   args = p.parse_args()
+  torch.manual_seed(0)  # same arguments -> same inputs, run to run
 
   from xotorch_amd.parallel.comm import init_distributed, max_over_ranks
   import torch.distributed as dist
@@ -126,6 +169,8 @@ def main():
   elapsed = time.perf_counter() - t0
   elapsed = max_over_ranks(elapsed, device if device == "cuda" else "cpu")
   ring.finish()
+  if args.dump_outputs and ring.is_last:
+    dump_outputs(ring, args.dump_outputs)
 
   tokens = global_batch * args.steps
   toks_per_s = tokens / elapsed

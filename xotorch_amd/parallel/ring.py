@@ -147,6 +147,9 @@ class RingPipeline:
     if not self.is_first:
       self.hid_buf = [torch.zeros(B, 1, D, dtype=dtype, device=device) for _ in range(self.M)]
     self.hid_out: List[Optional[torch.Tensor]] = [None] * self.M
+    # last stage: logits of the most recent decode step per micro-batch (under
+    # graphs this is the capture's static output, refreshed by every replay)
+    self.last_logits: List[Optional[torch.Tensor]] = [None] * self.M
     # async handles
     self._tok_recv_req = [None] * self.M
     self._tok_send_req = [None] * self.M
@@ -166,6 +169,7 @@ class RingPipeline:
       start_pos=-1, is_decode=True, seq_lens=self.seq_lens[mb],
     )
     if self.is_last:
+      self.last_logits[mb] = out
       tok = out.argmax(dim=-1, keepdim=True)  # greedy (reference default temp=0)
       if self.world == 1:
         self.tok_buf[mb].copy_(tok)  # wrap-around stays local
@@ -313,6 +317,12 @@ class RingPipeline:
       self._graphs[mb].replay()
     else:
       self._step_mb(mb)
+
+  def last_tokens(self) -> List[torch.Tensor]:
+    """Last stage: the [B, 1] token ids each micro-batch's most recent step
+    (prefill or decode) sampled — what the ring hands back to stage 0."""
+    assert self.is_last, "sampled tokens live on the last stage"
+    return self.tok_buf if self.world == 1 else self._tok_out
 
   def finish(self):
     """Drain outstanding async token traffic (call before teardown)."""
