@@ -199,6 +199,10 @@ def test_ops_linear_dispatch_matches(hip):
   (64, 28672, 8192, False),
   (256, 4096, 14336, False),
   (32, 1024, 128, False),
+  (32, 2048, 49152, False),  # 384 n-tiles: no split, kc = 2048 -> BK=128
+  (32, 32768, 128, False),   # one n-tile: nsplit = 16, kc = 2048 -> BK=128
+  (32, 32768, 128, True),    # same, bias applied in the combine
+  (32, 2112, 128, False),    # nsplit = 2, kc = 1088: ragged last split, 17 / 16 steps
 ])
 def test_skinny_gemm_packed(hip, M, K, N, bias):
   from xotorch_amd import ops as xops
@@ -225,7 +229,8 @@ def test_xotlinear_packed_matches_unpacked(hip):
   assert (y0 - y1).abs().max().item() / (y0.abs().max().item() + 1e-9) < 2e-2
 
 
-@pytest.mark.parametrize("E,C,K,N", [(8, 64, 512, 256), (128, 32, 256, 128)])
+@pytest.mark.parametrize("E,C,K,N", [(8, 64, 512, 256), (128, 32, 256, 128),
+                                     (2, 32, 2048, 128)])  # nsplit = 2: [nsplit, E*C, N] partials
 def test_skinny_gemm_grouped(hip, E, C, K, N):
   from xotorch_amd import ops as xops
   from xotorch_amd.ops import _hip_ops
@@ -373,6 +378,28 @@ def test_skinny_gemm_fp8(hip, M, K, N, bias):
   assert e2e < 0.12, e2e
 
 
+@pytest.mark.parametrize("E,M,K,N", [(2, 32, 512, 128),    # no split
+                                     (2, 32, 2048, 128)])  # nsplit = 2
+def test_skinny_gemm_fp8_grouped(hip, E, M, K, N):
+  """Grouped (E > 1) W8A8 kernel vs the per-expert quantize-dequantize fp32
+  reference: expert e reads its own weight block and its own sw[e*N:] scales."""
+  from xotorch_amd import ops as xops
+  from xotorch_amd.ops import _hip_ops
+  x = bt(E * M, K, scale=0.5, seed=E + M + N + 3)
+  ws = [bt(N, K, scale=0.02 * (e + 1), seed=K + 3 + e) for e in range(E)]
+  packed = [xops.pack_decode_weight_fp8(w) for w in ws]
+  wp8 = torch.stack([p[0] for p in packed]).contiguous()
+  sw = torch.stack([p[1] for p in packed]).contiguous()
+  x8, sx = _hip_ops.quant_fp8_rows(x)
+  got = _hip_ops.skinny_gemm_fp8(x8, sx, wp8, sw.view(-1), E, N, None).float().view(E, M, N)
+  x_deq = (x8.view(torch.float8_e4m3fn).float() * sx[:, None]).view(E, M, K)
+  for e in range(E):
+    w_deq = (ws[e].float() / sw[e][:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).float() * sw[e][:, None]
+    ref = torch.nn.functional.linear(x_deq[e], w_deq)
+    err = (got[e] - ref).abs().max().item() / (ref.abs().max().item() + 1e-9)
+    assert err < 2e-2, (e, err)
+
+
 def test_xotlinear_fp8_mode(hip, monkeypatch):
   from xotorch_amd.models.llama import XotLinear
   monkeypatch.setenv("XOT_FP8_GEMM", "1")
@@ -468,7 +495,8 @@ def test_rope_qkv_append_qk_norm(hip, hd, H, KVH, S):
 
 # ---------------- round 2: xreg GEMM + gemma2 attention semantics ----------------
 
-@pytest.mark.parametrize("M,K,N", [(64, 512, 256), (128, 4096, 1280), (128, 2048, 512), (256, 1024, 384)])
+@pytest.mark.parametrize("M,K,N", [(64, 512, 256), (128, 4096, 1280), (128, 2048, 512), (256, 1024, 384),
+                                   (32, 2112, 128)])  # nsplit = 2, kc = 1088: 17 / 16 steps
 def test_skinny_gemm_packed_xreg(hip, M, K, N):
   """v3 register-resident-X kernel vs torch matmul."""
   from xotorch_amd import ops
@@ -749,7 +777,9 @@ def test_moe_build_combine_kernels():
   assert torch.allclose(out, ref, atol=2e-2, rtol=2e-2), (out - ref).abs().max()
 
 
-@pytest.mark.parametrize("M,I,N", [(64, 512, 256), (128, 1024, 384), (96, 768, 128)])
+@pytest.mark.parametrize("M,I,N", [(64, 512, 256), (128, 1024, 384), (96, 768, 128),
+                                   (32, 2048, 128),    # nsplit = 2, BK=64
+                                   (32, 32768, 128)])  # nsplit = 16, kc = 2048 -> BK=128
 def test_skinny_gemm_packed_swiglu(hip, M, I, N):
   """Fused silu(gate)*up + down-GEMM vs the two-step reference."""
   from xotorch_amd import ops

@@ -1634,6 +1634,54 @@ DEVINL bf16x8 load_bf16x8(const unsigned short* p) {
   return *reinterpret_cast<const bf16x8*>(p);
 }
 
+// Shared epilogue of every skinny GEMM kernel: store one wave's MT 32x32
+// accumulators. D layout (32x32): m = lane&31 (col), n_local = (r&3) +
+// 8*(r>>2) + 4*(lane>>5). m0 = the lane's row in m-tile 0 (expert offset
+// included), nbase = the lane's first n. SPLIT writes fp32 partials into
+// P [nsplit, rows_total, N] (bias is added by the combine), otherwise bf16
+// + bias into Y. SCALED (fp8) dequantizes by sx[m] * sw[sw_base + n]
+// (sw_base = the expert's offset into sw); the bf16 kernels pass no scales.
+template <int MT, bool SPLIT, bool SCALED = false>
+DEVINL void skinny_store_acc(const floatx16 (&acc)[MT], unsigned short* Y, float* P,
+                             const unsigned short* bias, int N, int split, int rows_total,
+                             int m0, int nbase, const float* sx = nullptr,
+                             const float* sw = nullptr, size_t sw_base = 0) {
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int m = m0 + t * 32;
+    float sxm = 1.f;
+    if (SCALED) sxm = sx[m];
+    if (SPLIT) {
+      float* prow = P + ((size_t)split * rows_total + m) * N;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        floatx4 v4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          v4[j] = acc[t][g * 4 + j];
+          if (SCALED) v4[j] = v4[j] * sxm * sw[sw_base + nbase + g * 8 + j];
+        }
+        *reinterpret_cast<floatx4*>(prow + nbase + g * 8) = v4;
+      }
+    } else {
+      unsigned short* yrow = Y + (size_t)m * N;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        unsigned short o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float v = acc[t][g * 4 + j];
+          if (SCALED) v = v * sxm * sw[sw_base + nbase + g * 8 + j];
+          if (bias) v += b2f(bias[nbase + g * 8 + j]);
+          o[j] = f2b(v);
+        }
+        *reinterpret_cast<unsigned long long*>(yrow + nbase + g * 8) =
+            *reinterpret_cast<unsigned long long*>(o);
+      }
+    }
+  }
+}
+
 // MT = M/32 (1..8). One workgroup computes Y[0:M, n0:n0+128] over k-range
 // [k0, k1). Lane l of wave w holds A row (n0 + w*32 + (l&31)), k-chunk
 // (l>>5)*8; B col (mt*32 + (l&31)) of X with the same k-chunk.
@@ -1690,37 +1738,9 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
     xp += 16;
   }
 
-  // D layout (32x32): m = lane&31 (col), n_local = (r&3) + 8*(r>>2) + 4*(lane>>5)
-  const int m_local = lane & 31;
-  const int nbase = n0 + 4 * (lane >> 5);
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    const int m = t * 32 + m_local;
-    if (SPLIT) {
-      float* prow = P + ((size_t)split * (MT * 32) + m) * N;  // P layout [nsplit, M, N]
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        floatx4 v4;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v4[j] = acc[t][g * 4 + j];
-        *reinterpret_cast<floatx4*>(prow + nbase + g * 8) = v4;
-      }
-    } else {
-      unsigned short* yrow = Y + (size_t)m * N;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        unsigned short o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float v = acc[t][g * 4 + j];
-          if (bias) v += b2f(bias[nbase + g * 8 + j]);
-          o[j] = f2b(v);
-        }
-        *reinterpret_cast<unsigned long long*>(yrow + nbase + g * 8) =
-            *reinterpret_cast<unsigned long long*>(o);
-      }
-    }
-  }
+  // non-grouped: P layout [nsplit, M, N]
+  skinny_store_acc<MT, SPLIT>(acc, Y, P, bias, N, split, MT * 32, lane & 31,
+                              n0 + 4 * (lane >> 5));
 }
 
 // ---------------------------------------------------------------------------
@@ -1732,6 +1752,22 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
 // LDS image (row stride 72 elems = 144 B -> ds_read_b128 bank-conflict-free)
 // and read back as B fragments.  K % 64 == 0 required.
 // ---------------------------------------------------------------------------
+
+// One 16 B piece of the X stage. SWIGLU: p points at the gate half of the
+// fused [rows, 2K] gate|up row (up at +K); returns silu(gate) * up.
+template <bool SWIGLU>
+DEVINL ushort8 skinny_stage_load(const unsigned short* p, long long K) {
+  ushort8 v = *(const ushort8*)p;
+  if (SWIGLU) {
+    const ushort8 up = *(const ushort8*)(p + K);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float g = b2f(v[j]);
+      v[j] = f2b(g * __builtin_amdgcn_rcpf(1.f + __expf(-g)) * b2f(up[j]));
+    }
+  }
+  return v;
+}
 
 // Also the MoE grouped-GEMM kernel (the reference's latent
 // MOEExpert/MOELayer scaffolding, llm_utils.py:502-590, never executed): for
@@ -1795,17 +1831,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
   // prefetch keeps 2*BK*32n*2B per wave in flight across staging barriers.
   const unsigned short* wp1 = (nsteps > 1) ? wp + BKC * 512 : wp;  // clamp: no OOB at nsteps==1
 #pragma unroll
-  for (int i = 0; i < PPT; ++i) {
-    xv[i] = *(const ushort8*)(xpb + i * xstride_i);
-    if (SWIGLU) {
-      const ushort8 up = *(const ushort8*)(xpb + i * xstride_i + K);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float g = b2f(xv[i][j]);
-        xv[i][j] = f2b(g * __builtin_amdgcn_rcpf(1.f + __expf(-g)) * b2f(up[j]));
-      }
-    }
-  }
+  for (int i = 0; i < PPT; ++i) xv[i] = skinny_stage_load<SWIGLU>(xpb + i * xstride_i, K);
 #pragma unroll
   for (int u = 0; u < BKC; ++u) {
     a_buf[0][u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wp + u * 512));
@@ -1823,17 +1849,8 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
     const bool last = (s == nsteps - 1);                                                       \
     if (!last) {                                                                               \
       _Pragma("unroll")                                                                        \
-      for (int i = 0; i < PPT; ++i) {                                                          \
-        xv[i] = *(const ushort8*)(xpb + i * xstride_i + (size_t)(s + 1) * BK);                 \
-        if (SWIGLU) {                                                                          \
-          const ushort8 up_ = *(const ushort8*)(xpb + i * xstride_i + (size_t)(s + 1) * BK + K); \
-          _Pragma("unroll")                                                                    \
-          for (int j_ = 0; j_ < 8; ++j_) {                                                     \
-            const float g_ = b2f(xv[i][j_]);                                                   \
-            xv[i][j_] = f2b(g_ * __builtin_amdgcn_rcpf(1.f + __expf(-g_)) * b2f(up_[j_]));     \
-          }                                                                                    \
-        }                                                                                      \
-      }                                                                                        \
+      for (int i = 0; i < PPT; ++i)                                                            \
+        xv[i] = skinny_stage_load<SWIGLU>(xpb + i * xstride_i + (size_t)(s + 1) * BK, K);      \
     }                                                                                          \
     _Pragma("unroll")                                                                          \
     for (int u = 0; u < BKC; ++u) {                                                            \
@@ -1868,37 +1885,9 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
   if (s < nsteps) SGP_STEP(0);
 #undef SGP_STEP
 
-  const int m_local = lane & 31;
-  const int rows_total = gridDim.y * MT * 32;  // across all experts
-  const int nbase = tile * 128 + wv * 32 + 4 * (lane >> 5);
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    const int m = e * MT * 32 + t * 32 + m_local;
-    if (SPLIT) {
-      float* prow = P + ((size_t)split * rows_total + m) * N;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        floatx4 v4;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v4[j] = acc[t][g * 4 + j];
-        *reinterpret_cast<floatx4*>(prow + nbase + g * 8) = v4;
-      }
-    } else {
-      unsigned short* yrow = Y + (size_t)m * N;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        unsigned short o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float v = acc[t][g * 4 + j];
-          if (bias) v += b2f(bias[nbase + g * 8 + j]);
-          o[j] = f2b(v);
-        }
-        *reinterpret_cast<unsigned long long*>(yrow + nbase + g * 8) =
-            *reinterpret_cast<unsigned long long*>(o);
-      }
-    }
-  }
+  // rows_total spans all experts
+  skinny_store_acc<MT, SPLIT>(acc, Y, P, bias, N, split, gridDim.y * MT * 32,
+                              e * MT * 32 + (lane & 31), tile * 128 + wv * 32 + 4 * (lane >> 5));
 }
 
 // ---------------------------------------------------------------------------
@@ -1987,37 +1976,8 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_xreg_kernel(
   if (s < nsteps) XRG_STEP(0);
 #undef XRG_STEP
 
-  const int m_local = lane & 31;
-  const int rows_total = gridDim.y * MT * 32;
-  const int nbase = tile * 128 + wv * 32 + 4 * (lane >> 5);
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    const int m = e * MT * 32 + t * 32 + m_local;
-    if (SPLIT) {
-      float* prow = P + ((size_t)split * rows_total + m) * N;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        floatx4 v4;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v4[j] = acc[t][g * 4 + j];
-        *reinterpret_cast<floatx4*>(prow + nbase + g * 8) = v4;
-      }
-    } else {
-      unsigned short* yrow = Y + (size_t)m * N;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        unsigned short o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float v = acc[t][g * 4 + j];
-          if (bias) v += b2f(bias[nbase + g * 8 + j]);
-          o[j] = f2b(v);
-        }
-        *reinterpret_cast<unsigned long long*>(yrow + nbase + g * 8) =
-            *reinterpret_cast<unsigned long long*>(o);
-      }
-    }
-  }
+  skinny_store_acc<MT, SPLIT>(acc, Y, P, bias, N, split, gridDim.y * MT * 32,
+                              e * MT * 32 + (lane & 31), tile * 128 + wv * 32 + 4 * (lane >> 5));
 }
 
 // fp8 (OCP e4m3) W8A8 variant: same structure as the bf16 packed kernel but
@@ -2126,39 +2086,10 @@ __global__ __launch_bounds__(256) void skinny_gemm_fp8_kernel(
 #undef SGF_STEP
 
   // epilogue: dequantize acc * s_x[m] * s_w[n]
-  const int m_local = lane & 31;
-  const int rows_total = gridDim.y * MT * 32;
-  const int nbase = tile * 128 + wv * 32 + 4 * (lane >> 5);
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    const int m = e * MT * 32 + t * 32 + m_local;
-    const float sxm = sx[m];
-    if (SPLIT) {
-      float* prow = P + ((size_t)split * rows_total + m) * N;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        floatx4 v4;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          v4[j] = acc[t][g * 4 + j] * sxm * sw[(size_t)e * N + nbase + g * 8 + j];
-        *reinterpret_cast<floatx4*>(prow + nbase + g * 8) = v4;
-      }
-    } else {
-      unsigned short* yrow = Y + (size_t)m * N;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        unsigned short o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float v = acc[t][g * 4 + j] * sxm * sw[(size_t)e * N + nbase + g * 8 + j];
-          if (bias) v += b2f(bias[nbase + g * 8 + j]);
-          o[j] = f2b(v);
-        }
-        *reinterpret_cast<unsigned long long*>(yrow + nbase + g * 8) =
-            *reinterpret_cast<unsigned long long*>(o);
-      }
-    }
-  }
+  skinny_store_acc<MT, SPLIT, true>(acc, Y, P, bias, N, split, gridDim.y * MT * 32,
+                                    e * MT * 32 + (lane & 31),
+                                    tile * 128 + wv * 32 + 4 * (lane >> 5), sx, sw,
+                                    (size_t)e * N);
 }
 
 // per-row dynamic e4m3 quantization: x [M, K] bf16 -> x8 [M, K] + s_x [M]
@@ -2731,6 +2662,105 @@ torch::Tensor geglu_packed(torch::Tensor gu) {
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// Skinny decode GEMM launchers. The six bound functions below only check
+// their arguments and derive shapes; the split-K plan, the compile-time
+// kernel dispatch and the allocate / launch / combine sequence live here once.
+// ---------------------------------------------------------------------------
+
+struct SkinnyPlan {
+  int ntiles;  // 128-wide n-tiles
+  int nsplit;  // K splits; 1 = the kernel writes bf16 directly, no combine
+  int kc;      // k-range per split, a multiple of k_align
+  bool bk128;  // BK=128 staging (packed bf16 kernel only)
+};
+
+// E = experts sharing the launch (grid.y); k_align = 16 for the unpacked v1
+// kernel, 64 for everything on the prepack.
+static SkinnyPlan skinny_plan(long long N, long long K, long long E, int k_align, bool has_bk128) {
+  const int ntiles = (int)(N / 128);
+  // oversubscribe the 256 CUs (>=2 blocks/CU) while keeping K/SPLITK >= ~1024
+  int nsplit = 1;
+  while (ntiles * nsplit * E < skinny_target_blocks() && (K / (nsplit * 2)) >= 1024 && nsplit < 16) nsplit *= 2;
+  const int kc = (int)((K / nsplit + k_align - 1) / k_align * k_align);
+  while ((long long)kc * (nsplit - 1) >= K) nsplit--;  // drop empty splits
+  // BK=128 halves the staging-barrier count per byte; needs 128-aligned
+  // splits. The override is read per call (the GEMM race tool toggles it).
+  const bool bk128 = has_bk128 && (K % 128 == 0) && (kc % 128 == 0) && kc >= 2048
+                     && getenv("XOT_SKINNY_BK64") == nullptr;
+  return {ntiles, nsplit, kc, bk128};
+}
+
+template <int V>
+using IntC = std::integral_constant<int, V>;
+
+// runtime MT (1..8) -> f(IntC<MT>)
+template <class F>
+static void skinny_dispatch_mt(int MT, F&& f) {
+  switch (MT) {
+    case 1: f(IntC<1>{}); break;
+    case 2: f(IntC<2>{}); break;
+    case 3: f(IntC<3>{}); break;
+    case 4: f(IntC<4>{}); break;
+    case 5: f(IntC<5>{}); break;
+    case 6: f(IntC<6>{}); break;
+    case 7: f(IntC<7>{}); break;
+    case 8: f(IntC<8>{}); break;
+    default: TORCH_CHECK(false, "skinny GEMM: MT out of range");
+  }
+}
+
+// what a launcher's kernel call needs besides its own operands
+struct SkinnyLaunch {
+  dim3 grid;
+  hipStream_t stream;
+  unsigned short* Y;           // null when split
+  float* P;                    // null when not split
+  const unsigned short* bias;  // null when split (the combine adds it)
+  int kc, nsplit;
+};
+
+// Shared tail of every launcher: validate bias, allocate y (and the fp32
+// partials P [nsplit, E*rows, N] when split), launch the kernel that
+// `launch(mt, split, bk, L)` names with MT / SPLIT / BK as compile-time
+// constants, then combine. rows = rows per expert.
+template <bool HAS_BK128, class F>
+static torch::Tensor skinny_run(const torch::Tensor& x, at::IntArrayRef ysizes, long long rows,
+                                long long N, long long K, long long E,
+                                const c10::optional<torch::Tensor>& bias, int k_align, F&& launch) {
+  const unsigned short* bptr = nullptr;
+  if (bias.has_value()) {
+    CHK(bias->is_contiguous() && bias->dtype() == torch::kBFloat16 && bias->numel() == N);
+    bptr = (const unsigned short*)bias->data_ptr();
+  }
+  auto y = torch::empty(ysizes, x.options().dtype(torch::kBFloat16));
+  const SkinnyPlan p = skinny_plan(N, K, E, k_align, HAS_BK128);
+  const bool is_split = p.nsplit > 1;
+  torch::Tensor P;
+  if (is_split)
+    P = torch::empty({p.nsplit, (long)(E * rows), (long)N}, x.options().dtype(torch::kFloat32));
+  const SkinnyLaunch L{dim3(p.ntiles * p.nsplit, (unsigned)E), cur_stream(),
+                       is_split ? nullptr : (unsigned short*)y.data_ptr(),
+                       is_split ? P.data_ptr<float>() : nullptr,
+                       is_split ? nullptr : bptr, p.kc, p.nsplit};
+  skinny_dispatch_mt((int)(rows / 32), [&](auto mt) {
+    auto with_split = [&](auto split) {
+      if constexpr (HAS_BK128) {
+        if (p.bk128) return launch(mt, split, IntC<128>{}, L);
+      }
+      launch(mt, split, IntC<64>{}, L);
+    };
+    if (is_split) with_split(std::true_type{}); else with_split(std::false_type{});
+  });
+  if (is_split) {
+    const long long MN = E * rows * N;
+    const int blocks = (int)std::min<long long>(2048, (MN / 4 + 255) / 256);
+    hipLaunchKernelGGL(skinny_combine_kernel, dim3(blocks), dim3(256), 0, L.stream,
+                       P.data_ptr<float>(), (unsigned short*)y.data_ptr(), bptr, MN, N, p.nsplit);
+  }
+  return y;
+}
+
 // Y = x @ W^T (+bias). x: [M, K] bf16 contiguous rows (M <= 256, M % 32 == 0),
 // w: [N, K] bf16 contiguous, bias: optional [N] bf16.
 torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w,
@@ -2743,49 +2773,14 @@ torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w,
   CHK(x.is_contiguous());
   CHK(M >= 32 && M <= 256 && M % 32 == 0);
   CHK(N % 128 == 0 && K % 16 == 0);
-  const unsigned short* bptr = nullptr;
-  if (bias.has_value()) {
-    CHK(bias->is_contiguous() && bias->dtype() == torch::kBFloat16 && bias->numel() == N);
-    bptr = (const unsigned short*)bias->data_ptr();
-  }
   auto sizes = x.sizes().vec();
   sizes.back() = N;
-  auto y = torch::empty(sizes, x.options());
-  const int ntiles = N / 128;
-  // oversubscribe the 256 CUs (>=2 blocks/CU) while keeping K/SPLITK >= ~1024
-  int nsplit = 1;
-  while (ntiles * nsplit < skinny_target_blocks() && (K / (nsplit * 2)) >= 1024 && nsplit < 16) nsplit *= 2;
-  int kc = (int)((K / nsplit + 15) / 16 * 16);
-  while ((long long)kc * (nsplit - 1) >= K) nsplit--;  // drop empty splits
-  auto stream = cur_stream();
-  const int MT = (int)(M / 32);
-  const dim3 grid(ntiles * nsplit), block(256);
-#define SG_CASE(MTV) \
-  case MTV: \
-    if (nsplit == 1) { \
-      hipLaunchKernelGGL((skinny_gemm_kernel<MTV, false>), grid, block, 0, stream, \
-                         (const unsigned short*)w.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                         (unsigned short*)y.data_ptr(), nullptr, bptr, N, K, kc, nsplit); \
-    } else { \
-      hipLaunchKernelGGL((skinny_gemm_kernel<MTV, true>), grid, block, 0, stream, \
-                         (const unsigned short*)w.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                         nullptr, P.data_ptr<float>(), nullptr, N, K, kc, nsplit); \
-    } \
-    break;
-  if (nsplit == 1) {
-    torch::Tensor P;  // unused
-    switch (MT) { SG_CASE(1) SG_CASE(2) SG_CASE(3) SG_CASE(4) SG_CASE(5) SG_CASE(6) SG_CASE(7) SG_CASE(8) }
-  } else {
-    auto P = torch::empty({nsplit, M, (long long)N},
-                          torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
-    switch (MT) { SG_CASE(1) SG_CASE(2) SG_CASE(3) SG_CASE(4) SG_CASE(5) SG_CASE(6) SG_CASE(7) SG_CASE(8) }
-    const long long MN = M * (long long)N;
-    const int blocks = (int)std::min<long long>(2048, (MN / 4 + 255) / 256);
-    hipLaunchKernelGGL(skinny_combine_kernel, dim3(blocks), dim3(256), 0, stream,
-                       P.data_ptr<float>(), (unsigned short*)y.data_ptr(), bptr, MN, N, nsplit);
-  }
-#undef SG_CASE
-  return y;
+  return skinny_run<false>(x, sizes, M, N, K, 1, bias, 16,
+                           [&](auto mt, auto split, auto, const SkinnyLaunch& L) {
+    hipLaunchKernelGGL((skinny_gemm_kernel<mt.value, split.value>), L.grid, dim3(256), 0, L.stream,
+                       (const unsigned short*)w.data_ptr(), (const unsigned short*)x.data_ptr(),
+                       L.Y, L.P, L.bias, N, K, L.kc, L.nsplit);
+  });
 }
 
 // Packed variant. wp: the [N/32, K/16, 64, 8] prepack of w (see
@@ -2798,61 +2793,15 @@ torch::Tensor skinny_gemm_packed(torch::Tensor x, torch::Tensor wp, int64_t N,
   const long long M = x.numel() / K;
   CHK(M >= 32 && M <= 256 && M % 32 == 0);
   CHK(N % 128 == 0 && K % 64 == 0);
-  const unsigned short* bptr = nullptr;
-  if (bias.has_value()) {
-    CHK(bias->is_contiguous() && bias->dtype() == torch::kBFloat16 && bias->numel() == N);
-    bptr = (const unsigned short*)bias->data_ptr();
-  }
   auto sizes = x.sizes().vec();
   sizes.back() = (long)N;
-  auto y = torch::empty(sizes, x.options());
-  const int ntiles = (int)(N / 128);
-  int nsplit = 1;
-  while (ntiles * nsplit < skinny_target_blocks() && (K / (nsplit * 2)) >= 1024 && nsplit < 16) nsplit *= 2;
-  int kc = (int)((K / nsplit + 63) / 64 * 64);
-  while ((long long)kc * (nsplit - 1) >= K) nsplit--;
-  auto stream = cur_stream();
-  const int MT = (int)(M / 32);
-  // BK=128 halves the staging-barrier count per byte; needs 128-aligned splits
-  const bool bk128 = (K % 128 == 0) && (kc % 128 == 0) && kc >= 2048
-                     && getenv("XOT_SKINNY_BK64") == nullptr;
-  const dim3 grid(ntiles * nsplit), block(256);
-#define SGP_CASE(MTV) \
-  case MTV: \
-    if (nsplit == 1) { \
-      if (bk128) \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, false, 128>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                           (unsigned short*)y.data_ptr(), nullptr, bptr, (int)N, K, kc, nsplit); \
-      else \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, false, 64>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                           (unsigned short*)y.data_ptr(), nullptr, bptr, (int)N, K, kc, nsplit); \
-    } else { \
-      if (bk128) \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, true, 128>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                           nullptr, P.data_ptr<float>(), nullptr, (int)N, K, kc, nsplit); \
-      else \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, true, 64>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                           nullptr, P.data_ptr<float>(), nullptr, (int)N, K, kc, nsplit); \
-    } \
-    break;
-  if (nsplit == 1) {
-    torch::Tensor P;
-    switch (MT) { SGP_CASE(1) SGP_CASE(2) SGP_CASE(3) SGP_CASE(4) SGP_CASE(5) SGP_CASE(6) SGP_CASE(7) SGP_CASE(8) }
-  } else {
-    auto P = torch::empty({nsplit, M, (long long)N},
-                          torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
-    switch (MT) { SGP_CASE(1) SGP_CASE(2) SGP_CASE(3) SGP_CASE(4) SGP_CASE(5) SGP_CASE(6) SGP_CASE(7) SGP_CASE(8) }
-    const long long MN = M * (long long)N;
-    const int blocks = (int)std::min<long long>(2048, (MN / 4 + 255) / 256);
-    hipLaunchKernelGGL(skinny_combine_kernel, dim3(blocks), dim3(256), 0, stream,
-                       P.data_ptr<float>(), (unsigned short*)y.data_ptr(), bptr, MN, N, nsplit);
-  }
-#undef SGP_CASE
-  return y;
+  return skinny_run<true>(x, sizes, M, N, K, 1, bias, 64,
+                          [&](auto mt, auto split, auto bk, const SkinnyLaunch& L) {
+    hipLaunchKernelGGL((skinny_gemm_packed_kernel<mt.value, split.value, bk.value>),
+                       L.grid, dim3(256), 0, L.stream,
+                       (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(),
+                       L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit);
+  });
 }
 
 // v3 (register-resident X) launcher — same contract as skinny_gemm_packed.
@@ -2864,48 +2813,15 @@ torch::Tensor skinny_gemm_packed_xreg(torch::Tensor x, torch::Tensor wp, int64_t
   const long long M = x.numel() / K;
   CHK(M >= 32 && M <= 256 && M % 32 == 0);
   CHK(N % 128 == 0 && K % 64 == 0);
-  const unsigned short* bptr = nullptr;
-  if (bias.has_value()) {
-    CHK(bias->is_contiguous() && bias->dtype() == torch::kBFloat16 && bias->numel() == N);
-    bptr = (const unsigned short*)bias->data_ptr();
-  }
   auto sizes = x.sizes().vec();
   sizes.back() = (long)N;
-  auto y = torch::empty(sizes, x.options());
-  const int ntiles = (int)(N / 128);
-  int nsplit = 1;
-  while (ntiles * nsplit < skinny_target_blocks() && (K / (nsplit * 2)) >= 1024 && nsplit < 16) nsplit *= 2;
-  int kc = (int)((K / nsplit + 63) / 64 * 64);
-  while ((long long)kc * (nsplit - 1) >= K) nsplit--;
-  auto stream = cur_stream();
-  const int MT = (int)(M / 32);
-  const dim3 grid(ntiles * nsplit), block(256);
-#define SGX_CASE(MTV) \
-  case MTV: \
-    if (nsplit == 1) { \
-      hipLaunchKernelGGL((skinny_gemm_packed_xreg_kernel<MTV, false>), grid, block, 0, stream, \
-                         (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                         (unsigned short*)y.data_ptr(), nullptr, bptr, (int)N, K, kc, nsplit); \
-    } else { \
-      hipLaunchKernelGGL((skinny_gemm_packed_xreg_kernel<MTV, true>), grid, block, 0, stream, \
-                         (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                         nullptr, P.data_ptr<float>(), nullptr, (int)N, K, kc, nsplit); \
-    } \
-    break;
-  if (nsplit == 1) {
-    torch::Tensor P;
-    switch (MT) { SGX_CASE(1) SGX_CASE(2) SGX_CASE(3) SGX_CASE(4) SGX_CASE(5) SGX_CASE(6) SGX_CASE(7) SGX_CASE(8) }
-  } else {
-    auto P = torch::empty({nsplit, M, (long long)N},
-                          torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
-    switch (MT) { SGX_CASE(1) SGX_CASE(2) SGX_CASE(3) SGX_CASE(4) SGX_CASE(5) SGX_CASE(6) SGX_CASE(7) SGX_CASE(8) }
-    const long long MN = M * (long long)N;
-    const int blocks = (int)std::min<long long>(2048, (MN / 4 + 255) / 256);
-    hipLaunchKernelGGL(skinny_combine_kernel, dim3(blocks), dim3(256), 0, stream,
-                       P.data_ptr<float>(), (unsigned short*)y.data_ptr(), bptr, MN, N, nsplit);
-  }
-#undef SGX_CASE
-  return y;
+  return skinny_run<false>(x, sizes, M, N, K, 1, bias, 64,
+                           [&](auto mt, auto split, auto, const SkinnyLaunch& L) {
+    hipLaunchKernelGGL((skinny_gemm_packed_xreg_kernel<mt.value, split.value>),
+                       L.grid, dim3(256), 0, L.stream,
+                       (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(),
+                       L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit);
+  });
 }
 
 // Fused SwiGLU + down-projection decode GEMM: gu is the [M, 2K] fused
@@ -2921,61 +2837,16 @@ torch::Tensor skinny_gemm_packed_swiglu(torch::Tensor gu, torch::Tensor wp, int6
   CHK(gu.size(-1) == 2 * K);
   CHK(M >= 32 && M <= 256 && M % 32 == 0);
   CHK(N % 128 == 0 && K % 64 == 0);
-  const unsigned short* bptr = nullptr;
-  if (bias.has_value()) {
-    CHK(bias->is_contiguous() && bias->dtype() == torch::kBFloat16 && bias->numel() == N);
-    bptr = (const unsigned short*)bias->data_ptr();
-  }
   auto sizes = gu.sizes().vec();
   sizes.back() = (long)N;
-  auto y = torch::empty(sizes, gu.options());
-  const int ntiles = (int)(N / 128);
-  int nsplit = 1;
-  while (ntiles * nsplit < skinny_target_blocks() && (K / (nsplit * 2)) >= 1024 && nsplit < 16) nsplit *= 2;
-  int kc = (int)((K / nsplit + 63) / 64 * 64);
-  while ((long long)kc * (nsplit - 1) >= K) nsplit--;
-  auto stream = cur_stream();
-  const int MT = (int)(M / 32);
-  const bool bk128 = (K % 128 == 0) && (kc % 128 == 0) && kc >= 2048
-                     && getenv("XOT_SKINNY_BK64") == nullptr;
-  const dim3 grid(ntiles * nsplit), block(256);
   const long long ldx = 2 * K;
-#define SGS_CASE(MTV) \
-  case MTV: \
-    if (nsplit == 1) { \
-      if (bk128) \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, false, 128, true>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)gu.data_ptr(), \
-                           (unsigned short*)y.data_ptr(), nullptr, bptr, (int)N, K, kc, nsplit, ldx); \
-      else \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, false, 64, true>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)gu.data_ptr(), \
-                           (unsigned short*)y.data_ptr(), nullptr, bptr, (int)N, K, kc, nsplit, ldx); \
-    } else { \
-      if (bk128) \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, true, 128, true>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)gu.data_ptr(), \
-                           nullptr, P.data_ptr<float>(), nullptr, (int)N, K, kc, nsplit, ldx); \
-      else \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, true, 64, true>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)gu.data_ptr(), \
-                           nullptr, P.data_ptr<float>(), nullptr, (int)N, K, kc, nsplit, ldx); \
-    } \
-    break;
-  if (nsplit == 1) {
-    torch::Tensor P;
-    switch (MT) { SGS_CASE(1) SGS_CASE(2) SGS_CASE(3) SGS_CASE(4) SGS_CASE(5) SGS_CASE(6) SGS_CASE(7) SGS_CASE(8) }
-  } else {
-    auto P = torch::empty({nsplit, M, (long long)N},
-                          torch::TensorOptions().dtype(torch::kFloat32).device(gu.device()));
-    switch (MT) { SGS_CASE(1) SGS_CASE(2) SGS_CASE(3) SGS_CASE(4) SGS_CASE(5) SGS_CASE(6) SGS_CASE(7) SGS_CASE(8) }
-    const long long MN = M * (long long)N;
-    const int blocks = (int)std::min<long long>(2048, (MN / 4 + 255) / 256);
-    hipLaunchKernelGGL(skinny_combine_kernel, dim3(blocks), dim3(256), 0, stream,
-                       P.data_ptr<float>(), (unsigned short*)y.data_ptr(), bptr, MN, N, nsplit);
-  }
-#undef SGS_CASE
-  return y;
+  return skinny_run<true>(gu, sizes, M, N, K, 1, bias, 64,
+                          [&](auto mt, auto split, auto bk, const SkinnyLaunch& L) {
+    hipLaunchKernelGGL((skinny_gemm_packed_kernel<mt.value, split.value, bk.value, true>),
+                       L.grid, dim3(256), 0, L.stream,
+                       (const unsigned short*)wp.data_ptr(), (const unsigned short*)gu.data_ptr(),
+                       L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit, ldx);
+  });
 }
 
 // MoE grouped decode GEMM: x [E, C, K] (C = per-expert token capacity,
@@ -2988,53 +2859,13 @@ torch::Tensor skinny_gemm_grouped(torch::Tensor x, torch::Tensor wp, int64_t E, 
   const long long C = x.numel() / (K * E);
   CHK(C >= 32 && C <= 256 && C % 32 == 0);
   CHK(N % 128 == 0 && K % 64 == 0 && E >= 1 && E <= 256);
-  auto y = torch::empty({(long)E, (long)C, (long)N}, x.options());
-  const int ntiles = (int)(N / 128);
-  int nsplit = 1;
-  while (ntiles * nsplit * E < skinny_target_blocks() && (K / (nsplit * 2)) >= 1024 && nsplit < 16) nsplit *= 2;
-  int kc = (int)((K / nsplit + 63) / 64 * 64);
-  while ((long long)kc * (nsplit - 1) >= K) nsplit--;
-  auto stream = cur_stream();
-  const int MT = (int)(C / 32);
-  const dim3 grid(ntiles * nsplit, (unsigned)E), block(256);
-  const bool bk128 = (K % 128 == 0) && (kc % 128 == 0) && kc >= 2048
-                     && getenv("XOT_SKINNY_BK64") == nullptr;
-#define SGG_CASE(MTV) \
-  case MTV: \
-    if (nsplit == 1) { \
-      if (bk128) \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, false, 128>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                           (unsigned short*)y.data_ptr(), nullptr, nullptr, (int)N, K, kc, nsplit); \
-      else \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, false, 64>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                           (unsigned short*)y.data_ptr(), nullptr, nullptr, (int)N, K, kc, nsplit); \
-    } else { \
-      if (bk128) \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, true, 128>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                           nullptr, P.data_ptr<float>(), nullptr, (int)N, K, kc, nsplit); \
-      else \
-        hipLaunchKernelGGL((skinny_gemm_packed_kernel<MTV, true, 64>), grid, block, 0, stream, \
-                           (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(), \
-                           nullptr, P.data_ptr<float>(), nullptr, (int)N, K, kc, nsplit); \
-    } \
-    break;
-  if (nsplit == 1) {
-    torch::Tensor P;
-    switch (MT) { SGG_CASE(1) SGG_CASE(2) SGG_CASE(3) SGG_CASE(4) SGG_CASE(5) SGG_CASE(6) SGG_CASE(7) SGG_CASE(8) }
-  } else {
-    auto P = torch::empty({nsplit, (long)(E * C), (long)N},
-                          torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
-    switch (MT) { SGG_CASE(1) SGG_CASE(2) SGG_CASE(3) SGG_CASE(4) SGG_CASE(5) SGG_CASE(6) SGG_CASE(7) SGG_CASE(8) }
-    const long long MN = E * C * N;
-    const int blocks = (int)std::min<long long>(2048, (MN / 4 + 255) / 256);
-    hipLaunchKernelGGL(skinny_combine_kernel, dim3(blocks), dim3(256), 0, stream,
-                       P.data_ptr<float>(), (unsigned short*)y.data_ptr(), nullptr, MN, N, nsplit);
-  }
-#undef SGG_CASE
-  return y;
+  return skinny_run<true>(x, {(long)E, (long)C, (long)N}, C, N, K, E, c10::nullopt, 64,
+                          [&](auto mt, auto split, auto bk, const SkinnyLaunch& L) {
+    hipLaunchKernelGGL((skinny_gemm_packed_kernel<mt.value, split.value, bk.value>),
+                       L.grid, dim3(256), 0, L.stream,
+                       (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(),
+                       L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit);
+  });
 }
 
 // x: [M, K] bf16 -> (x8 uint8 [M, K], s_x fp32 [M])
@@ -3065,49 +2896,14 @@ torch::Tensor skinny_gemm_fp8(torch::Tensor x8, torch::Tensor sx, torch::Tensor 
   const long long M = x8.numel() / (K * E);  // rows per expert
   CHK(M >= 32 && M <= 256 && M % 32 == 0);
   CHK(N % 128 == 0 && K % 64 == 0 && sw.numel() == E * N && sx.numel() == E * M);
-  const unsigned short* bptr = nullptr;
-  if (bias.has_value()) {
-    CHK(bias->is_contiguous() && bias->dtype() == torch::kBFloat16 && bias->numel() == N);
-    bptr = (const unsigned short*)bias->data_ptr();
-  }
-  auto y = torch::empty({(long)(E * M), (long)N},
-                        torch::TensorOptions().dtype(torch::kBFloat16).device(x8.device()));
-  const int ntiles = (int)(N / 128);
-  int nsplit = 1;
-  while (ntiles * nsplit * E < skinny_target_blocks() && (K / (nsplit * 2)) >= 1024 && nsplit < 16) nsplit *= 2;
-  int kc = (int)((K / nsplit + 63) / 64 * 64);
-  while ((long long)kc * (nsplit - 1) >= K) nsplit--;
-  auto stream = cur_stream();
-  const int MT = (int)(M / 32);
-  const dim3 grid(ntiles * nsplit, (unsigned)E), block(256);
-#define SGF_CASE(MTV) \
-  case MTV: \
-    if (nsplit == 1) { \
-      hipLaunchKernelGGL((skinny_gemm_fp8_kernel<MTV, false>), grid, block, 0, stream, \
-                         (const unsigned char*)wp8.data_ptr(), (const unsigned char*)x8.data_ptr(), \
-                         sw.data_ptr<float>(), sx.data_ptr<float>(), \
-                         (unsigned short*)y.data_ptr(), nullptr, bptr, (int)N, K, kc, nsplit); \
-    } else { \
-      hipLaunchKernelGGL((skinny_gemm_fp8_kernel<MTV, true>), grid, block, 0, stream, \
-                         (const unsigned char*)wp8.data_ptr(), (const unsigned char*)x8.data_ptr(), \
-                         sw.data_ptr<float>(), sx.data_ptr<float>(), \
-                         nullptr, P.data_ptr<float>(), nullptr, (int)N, K, kc, nsplit); \
-    } \
-    break;
-  if (nsplit == 1) {
-    torch::Tensor P;
-    switch (MT) { SGF_CASE(1) SGF_CASE(2) SGF_CASE(3) SGF_CASE(4) SGF_CASE(5) SGF_CASE(6) SGF_CASE(7) SGF_CASE(8) }
-  } else {
-    auto P = torch::empty({nsplit, (long)(E * M), (long)N},
-                          torch::TensorOptions().dtype(torch::kFloat32).device(x8.device()));
-    switch (MT) { SGF_CASE(1) SGF_CASE(2) SGF_CASE(3) SGF_CASE(4) SGF_CASE(5) SGF_CASE(6) SGF_CASE(7) SGF_CASE(8) }
-    const long long MN = E * M * N;
-    const int blocks = (int)std::min<long long>(2048, (MN / 4 + 255) / 256);
-    hipLaunchKernelGGL(skinny_combine_kernel, dim3(blocks), dim3(256), 0, stream,
-                       P.data_ptr<float>(), (unsigned short*)y.data_ptr(), bptr, MN, N, nsplit);
-  }
-#undef SGF_CASE
-  return y;
+  return skinny_run<false>(x8, {(long)(E * M), (long)N}, M, N, K, E, bias, 64,
+                           [&](auto mt, auto split, auto, const SkinnyLaunch& L) {
+    hipLaunchKernelGGL((skinny_gemm_fp8_kernel<mt.value, split.value>),
+                       L.grid, dim3(256), 0, L.stream,
+                       (const unsigned char*)wp8.data_ptr(), (const unsigned char*)x8.data_ptr(),
+                       sw.data_ptr<float>(), sx.data_ptr<float>(),
+                       L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit);
+  });
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
