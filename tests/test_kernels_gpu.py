@@ -1105,3 +1105,212 @@ def test_deepseek_yarn_gpu_matches_eager():
       assert torch.allclose(lg.float().cpu(), lr.float(), atol=0.5, rtol=0.1), \
         (step, (lg.float().cpu() - lr.float()).abs().max())
       nxt = lg.argmax(-1, keepdim=True)
+
+
+# ---------------- attention / append paths the shared device helpers cover ----------------
+
+def _unpack_k(kp, t32):
+  """Inverse of _pack_k: [B,KVH,t32/16,4,64,8] -> [B,KVH,t32,128]."""
+  B, KVH = kp.shape[:2]
+  return kp.view(B, KVH, t32 // 16, 4, 4, 16, 8).permute(0, 1, 2, 5, 3, 4, 6).reshape(B, KVH, t32, 128)
+
+
+def _unpack_v(vp, t32):
+  """Inverse of _pack_v: [B,KVH,8,t32/32,64,8] -> [B,KVH,t32,128]."""
+  B, KVH = vp.shape[:2]
+  return vp.view(B, KVH, 8, t32 // 32, 4, 16, 8).permute(0, 1, 3, 4, 6, 2, 5).reshape(B, KVH, t32, 128)
+
+
+def _e4m3_bound(x, scale):
+  """|dequant - x| bound for an e4m3 row quantized at `scale`: 3 mantissa bits
+  (2^-4 relative), x itself a bf16 rounding of the quantized fp32 value
+  (2^-8 relative), smallest subnormal 2^-9 in units of the scale."""
+  return (2.0 ** -4 + 2.0 ** -8) * x.abs() + scale * 2.0 ** -9
+
+
+@pytest.fixture(scope="module")
+def gqa_caches(hip):
+  """One rope_qkv_append of 100 positions into T=128 caches (B=2, H=8, KVH=2),
+  bf16-packed and fp8-packed, plus the decode query of the last position."""
+  from xotorch_amd.ops import _hip_ops
+  from xotorch_amd.ops.torch_ref import rope_cos_sin
+  B, S, H, KVH, hd, T = 2, 100, 8, 2, 128, 128
+  qkv = bt(B, S, (H + 2 * KVH) * hd, seed=171, scale=0.5)
+  qkv8 = qkv.clone()
+  kc = torch.zeros(B, KVH, T, hd, dtype=torch.bfloat16, device="cuda")
+  vc = torch.zeros_like(kc)
+  kp8 = torch.zeros(B, KVH, T // 16, 4, 64, 8, dtype=torch.uint8, device="cuda")
+  vp8 = torch.zeros(B, KVH, 8, T // 32, 64, 8, dtype=torch.uint8, device="cuda")
+  ksc = torch.ones(B, KVH, T, dtype=torch.float32, device="cuda")
+  vsc = torch.ones_like(ksc)
+  cos, sin = rope_cos_sin(hd, T, 10000.0, device="cuda")
+  pos = torch.arange(S, dtype=torch.int32, device="cuda")
+  _hip_ops.rope_qkv_append(qkv, cos, sin, pos, kc, vc, H, KVH, hd)
+  _hip_ops.rope_qkv_append(qkv8, cos, sin, pos, kc.clone(), vc.clone(), H, KVH, hd, kp8, vp8,
+                           k_scale=ksc, v_scale=vsc)
+  q = qkv[:, -1:, : H * hd].view(B, 1, H, hd).contiguous()
+  return dict(q=q, kc=kc, vc=vc, kp=_pack_k(kc, T), vp=_pack_v(vc, T),
+              kp8=kp8, vp8=vp8, ksc=ksc, vsc=vsc, T=T)
+
+
+@pytest.mark.parametrize("fp8", [False, True])
+def test_attn_decode_mfma_prefetch_off_equals_on(hip, gqa_caches, monkeypatch, fp8):
+  """XOT_ATTN_PREFETCH moves the K loads, not the arithmetic: both settings
+  give the same bits. seq_lens [33, 100] at T=128 -> nsplit 4, chunk 32, so
+  batch 0 has one full split, a one-position split and two empty splits."""
+  from xotorch_amd.ops import _hip_ops, torch_ref
+  c = gqa_caches
+  sls = [33, 100]
+  sl_t = torch.tensor(sls, dtype=torch.int32, device="cuda")
+  def run():
+    if fp8:
+      return _hip_ops.attn_decode_mfma(c["q"], c["kp8"], c["vp8"], sl_t, c["T"],
+                                       k_scale=c["ksc"], v_scale=c["vsc"])
+    return _hip_ops.attn_decode_mfma(c["q"], c["kp"], c["vp"], sl_t, c["T"])
+  monkeypatch.setenv("XOT_ATTN_PREFETCH", "0")
+  off = run()
+  monkeypatch.delenv("XOT_ATTN_PREFETCH")
+  on = run()
+  assert torch.equal(off, on)
+  for b, s in enumerate(sls):
+    ref = torch_ref.attn_decode(c["q"][b:b + 1], c["kc"][b:b + 1, :, :s], c["vc"][b:b + 1, :, :s], s).float()
+    o = on[b:b + 1].float()
+    err = (o - ref).abs().max().item()
+    print(f"fp8={fp8} b={b} sl={s} max abs err {err:.4g} ref max {ref.abs().max().item():.4g}")
+    if fp8:
+      assert err < 0.12 * max(ref.abs().max().item(), 1.0) + 0.05, (b, err)
+    else:
+      assert torch.allclose(o, ref, atol=3e-2, rtol=3e-2), (b, err)
+
+
+def test_fp8_kv_append_content(hip):
+  """The fp8 packed copies themselves (not just the decode through them):
+  dequantized bytes match the plain cache rows within the e4m3 bound, scales
+  are rowmax/448, unwritten positions stay zero with scale 1."""
+  from xotorch_amd.ops import _hip_ops
+  from xotorch_amd.ops.torch_ref import rope_cos_sin
+  B, S, H, KVH, hd, T = 2, 40, 8, 4, 128, 64
+  qkv = bt(B, S, (H + 2 * KVH) * hd, seed=141, scale=0.5)
+  kc = torch.zeros(B, KVH, T, hd, dtype=torch.bfloat16, device="cuda")
+  vc = torch.zeros_like(kc)
+  kp8 = torch.zeros(B, KVH, T // 16, 4, 64, 8, dtype=torch.uint8, device="cuda")
+  vp8 = torch.zeros(B, KVH, 8, T // 32, 64, 8, dtype=torch.uint8, device="cuda")
+  ksc = torch.ones(B, KVH, T, dtype=torch.float32, device="cuda")
+  vsc = torch.ones_like(ksc)
+  cos, sin = rope_cos_sin(hd, T, 10000.0, device="cuda")
+  pos = torch.arange(S, dtype=torch.int32, device="cuda")
+  _hip_ops.rope_qkv_append(qkv, cos, sin, pos, kc, vc, H, KVH, hd, kp8, vp8,
+                           k_scale=ksc, v_scale=vsc)
+  for name, p8, sc, plain, unpack in (("k", kp8, ksc, kc, _unpack_k), ("v", vp8, vsc, vc, _unpack_v)):
+    deq = unpack(p8.view(torch.float8_e4m3fn), T).float() * sc[..., None]
+    x = plain.float()
+    excess = ((deq - x).abs() - _e4m3_bound(x, sc[..., None]))[:, :, :S].max().item()
+    rowmax = x[:, :, :S].abs().amax(dim=-1)
+    srel = (sc[:, :, :S] * 448.0 / rowmax - 1.0).abs().max().item()
+    print(f"{name}: max (err - bound) {excess:.4g}, scale rel err {srel:.4g}")
+    assert excess <= 0.0, (name, excess)
+    assert srel <= 2.0 ** -8, (name, srel)
+    assert (unpack(p8, T)[:, :, S:] == 0).all() and (sc[:, :, S:] == 1.0).all()
+
+
+def test_mla_fp8_append_content(hip):
+  """mla_prep_append fp8 mode: dequantized kp8/vp8 against _mla_pack_ref of
+  the plain latent/rope rows, one scale per token over all 576 dims."""
+  from xotorch_amd.ops import _hip_ops
+  from xotorch_amd.ops.torch_ref import rope_cos_sin
+  B, S, T = 2, 40, 64
+  ckv = bt(B, S, 576, seed=161, scale=0.5)
+  w = bt(512, seed=162, scale=0.3) + 1.0
+  cos, sin = rope_cos_sin(64, T, 10000.0, device="cuda")
+  pos = torch.arange(S, dtype=torch.int32, device="cuda")
+  lat_c = torch.zeros(B, 1, T, 512, dtype=torch.bfloat16, device="cuda")
+  rot_c = torch.zeros(B, 1, T, 64, dtype=torch.bfloat16, device="cuda")
+  kp8 = torch.zeros(B, T // 16, 18, 64, 8, dtype=torch.uint8, device="cuda")
+  vp8 = torch.zeros(B, 32, T // 32, 64, 8, dtype=torch.uint8, device="cuda")
+  ks = torch.ones(B, T, dtype=torch.float32, device="cuda")
+  _hip_ops.mla_prep_append(ckv, w.contiguous(), cos, sin, pos, lat_c, rot_c, kp8, vp8, 1e-6, False, ks)
+  lat, rot = lat_c[:, 0, :S].float(), rot_c[:, 0, :S].float()
+  rowmax = torch.cat([lat, rot], dim=-1).abs().amax(dim=-1)
+  srel = (ks[:, :S] * 448.0 / rowmax - 1.0).abs().max().item()
+  # one packer pass carries the values (batch rows 0..B-1) and their scales (B..2B-1)
+  sc = ks[:, :S, None]
+  kp_ref, vp_ref = _mla_pack_ref(torch.cat([lat, sc.expand(B, S, 512)]),
+                                 torch.cat([rot, sc.expand(B, S, 64)]), T)
+  for name, p8, ref in (("k", kp8, kp_ref), ("v", vp8, vp_ref)):
+    deq = p8.view(torch.float8_e4m3fn).float() * ref[B:]
+    excess = ((deq - ref[:B]).abs() - _e4m3_bound(ref[:B], ref[B:])).max().item()
+    print(f"mla {name}: max (err - bound) {excess:.4g}, scale rel err {srel:.4g}")
+    assert excess <= 0.0, (name, excess)
+    assert (p8[ref[B:] == 0] == 0).all()  # nothing written outside the S rows
+  assert srel <= 2.0 ** -8, srel
+  assert (ks[:, S:] == 1.0).all()
+
+
+def test_attn_decode_mfma_fp8_softcap_window(hip, gqa_caches):
+  """fp8 cache with gemma2 flags vs the bf16 packed path with the same flags."""
+  from xotorch_amd.ops import _hip_ops
+  c = gqa_caches
+  sl_t = torch.full((2,), 100, dtype=torch.int32, device="cuda")
+  ref = _hip_ops.attn_decode_mfma(c["q"], c["kp"], c["vp"], sl_t, c["T"], 0.0, 30.0, 40).float()
+  out = _hip_ops.attn_decode_mfma(c["q"], c["kp8"], c["vp8"], sl_t, c["T"], 0.0, 30.0, 40,
+                                  k_scale=c["ksc"], v_scale=c["vsc"]).float()
+  err = (out - ref).abs().max().item()
+  print(f"max abs err {err:.4g} ref max {ref.abs().max().item():.4g}")
+  assert err < 0.12 * max(ref.abs().max().item(), 1.0) + 0.05, err
+
+
+def test_attn_decode_mla_partial_head_group(hip):
+  """H=20: head groups of 16 and 4 (clamped q rows, predicated partial store)."""
+  test_attn_decode_mla_vs_ref(hip, 1, 20, 64, 50)
+
+
+def test_attn_decode_two_head_slices_hd64(hip):
+  """12 q heads per kv head at hd=64: partial launches NQ=8 then NQ=4 (qh0=8)."""
+  test_attn_decode(hip, 64, 24, 2, 1, 64, 50)
+
+
+def test_rope_qkv_append_per_row_positions_packed(hip):
+  """Per-row positions (numel B*S != S) with q/k norm into the packed bf16
+  caches: each batch row lands at its own position in every layout."""
+  from xotorch_amd.ops import _hip_ops, torch_ref
+  B, S, H, KVH, hd, T = 2, 1, 4, 2, 128, 64
+  qkv = bt(B, S, (H + 2 * KVH) * hd, seed=181)
+  qkv_ref = qkv.clone()
+  cos, sin = torch_ref.rope_cos_sin(hd, T, 1000000.0, device="cuda")
+  kc = torch.zeros(B, KVH, T, hd, dtype=torch.bfloat16, device="cuda")
+  vc = torch.zeros_like(kc)
+  kc_ref, vc_ref = kc.clone(), vc.clone()
+  kp = torch.zeros(B, KVH, T // 16, 4, 64, 8, dtype=torch.bfloat16, device="cuda")
+  vp = torch.zeros(B, KVH, 8, T // 32, 64, 8, dtype=torch.bfloat16, device="cuda")
+  qn = (torch.randn(hd, device="cuda") * 0.2 + 1.0).to(torch.bfloat16)
+  kn = (torch.randn(hd, device="cuda") * 0.2 + 1.0).to(torch.bfloat16)
+  rows = [5, 37]
+  pos = torch.tensor(rows, dtype=torch.int32, device="cuda")
+  _hip_ops.rope_qkv_append(qkv, cos, sin, pos, kc, vc, H, KVH, hd, kp, vp, qn, kn, 1e-6)
+  assert torch.equal(kp, _pack_k(kc, T))
+  assert torch.equal(vp, _pack_v(vc, T))
+  for b, r in enumerate(rows):
+    others = [t for t in range(T) if t != r]
+    assert (kc[b, :, others] == 0).all() and (vc[b, :, others] == 0).all()
+    assert (kc[b, :, r] != 0).any() and (vc[b, :, r] != 0).any()
+  torch_ref.rope_qkv_append(qkv_ref, cos, sin, pos, kc_ref, vc_ref, H, KVH, hd, qn, kn, 1e-6)
+  assert torch.allclose(qkv.float(), qkv_ref.float(), atol=3e-2, rtol=3e-2)
+  assert torch.allclose(kc.float(), kc_ref.float(), atol=3e-2, rtol=3e-2)
+  assert torch.equal(vc, vc_ref)
+
+
+def test_attn_prefill_mfma_window_tile_skip(hip):
+  """start_pos 96, window 48: the first kv tile lies wholly below the window
+  and is skipped (tp0 = 1); S = 40 is no multiple of the 16-row sub-tile."""
+  from xotorch_amd.ops import _hip_ops, torch_ref
+  B, H, KVH, S, hd, start, window = 1, 4, 2, 40, 128, 96, 48
+  scale = 1.0 / 16.0
+  total = start + S
+  t32 = 160
+  q = bt(B, S, H, hd, seed=91)
+  k = bt(B, KVH, total, hd, seed=92)
+  v = bt(B, KVH, total, hd, seed=93)
+  kp, vp = _pack_k(k, t32), _pack_v(v, t32)
+  out = _hip_ops.attn_prefill_mfma(q, kp, vp, start, scale, 0.0, window).float()
+  ref = torch_ref.attn_prefill(q, k, v, start, S, scale, 0.0, window).float()
+  assert torch.allclose(out, ref, atol=3e-2, rtol=3e-2), (out - ref).abs().max()

@@ -56,6 +56,79 @@ DEVINL unsigned short f2b(float f) {
 }
 
 // ---------------------------------------------------------------------------
+// Device helpers shared by the norm, KV-append and attention kernels
+// ---------------------------------------------------------------------------
+
+// 64-lane xor-butterfly reductions; every lane ends with the wave's value
+DEVINL float wave_sum(float v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+DEVINL float wave_max(float v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+  return v;
+}
+
+// MFMA-fragment-packed KV cache — the ONE definition of the two layouts
+// (the tests' _pack_k / _pack_v / _mla_pack_ref state them independently).
+// A fragment is 64 lanes x 8 elements (bf16, or e4m3 bytes in fp8 mode) and is
+// what one v_mfma_f32_16x16x32 B operand reads: the attention kernels stream
+// it lane-linearly (lane * 8), one coalesced wave load per fragment.
+//   K image of a head: [pos>>4][d>>5][lane][d&7],  lane = ((d&31)>>3)*16 + (pos&15)
+//     a 16-position tile holds dims/32 fragments: 4 for GQA hd=128, 18 for MLA
+//   V image of a head: [d>>4][pos>>5][lane][pos&7], lane = ((pos&31)>>3)*16 + (d&15)
+//     one fragment per (16-dim group, 32-position tile): 8 groups GQA, 32 MLA
+constexpr int FRAG = 512;            // elements per fragment
+constexpr int GQA_KTILE = 4 * FRAG;  // one 16-position K tile at hd = 128
+constexpr int GQA_VGROUPS = 8;       // 16-dim V groups at hd = 128
+
+// offset of (dim d, position pos) inside its 16-position K tile
+DEVINL size_t kfrag_off(int d, int pos) {
+  return (size_t)(d >> 5) * FRAG + (((d & 31) >> 3) * 16 + (pos & 15)) * 8 + (d & 7);
+}
+
+// offset of (dim d, position pos) inside a head's V image of tiles32 32-position tiles
+DEVINL size_t vfrag_off(int d, int pos, int tiles32) {
+  return ((size_t)(d >> 4) * tiles32 + (pos >> 5)) * FRAG + (((pos & 31) >> 3) * 16 + (d & 15)) * 8 + (pos & 7);
+}
+
+// OCP e4m3 quantization: scale = amax / 448 (floored so 1/scale is finite)
+DEVINL float e4m3_scale(float amax) { return fmaxf(amax, 1e-12f) / 448.f; }
+
+DEVINL unsigned short to_e4m3x2(float a, float b) {
+  return (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+}
+
+DEVINL unsigned char to_e4m3(float v) { return (unsigned char)(to_e4m3x2(v, 0.f) & 0xff); }
+
+// 8 bf16 (one MFMA fragment, or 16 B of a row) times inv -> 8 e4m3 bytes
+DEVINL long to_e4m3x8(bf16x8 v, float inv) {
+  unsigned char o[8];
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    const unsigned short pk = to_e4m3x2((float)v[j] * inv, (float)v[j + 1] * inv);
+    o[j] = (unsigned char)(pk & 0xff);
+    o[j + 1] = (unsigned char)(pk >> 8);
+  }
+  return *reinterpret_cast<const long*>(o);
+}
+
+// positions: [S] (shared across batch) or [B*S] (per-row — continuous
+// batching where every slot decodes at its own position); bs = b * S + s
+DEVINL int row_position(const int* __restrict__ positions, int npos, int B, int S, int bs) {
+  return positions[(npos == B * S && npos != S) ? bs : bs % S];
+}
+
+// HF rotate-half on one (x1, x2) pair -> (r1, r2) = (x1 c - x2 s, x2 c + x1 s)
+DEVINL void rope_pair(float x1, float x2, float c, float sn, float& r1, float& r2) {
+  r1 = x1 * c - x2 * sn;
+  r2 = x2 * c + x1 * sn;
+}
+
+// ---------------------------------------------------------------------------
 // RMSNorm (optionally fused with residual add)
 // one workgroup per row; 256 threads; row cached in registers between the
 // two passes (up to 8 chunks of 8 bf16 per thread -> D <= 16384)
@@ -97,8 +170,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(
     }
   }
   // wave reduce then cross-wave through LDS
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m);
+  acc = wave_sum(acc);
   __shared__ float red[4];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
@@ -128,15 +200,40 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(
 
 // When the MFMA-packed cache copies exist (kpc/vpc non-null, hd == 128) the
 // same kernel also appends into them (decode attention then streams the
-// cache as coalesced v_mfma_f32_16x16x32_bf16 B-fragments):
-//   K_packed [B,KVH][T32/16 tile][4 hd-chunk][64 lane][8]  lane=(hd&31)/8*16 + (pos&15)
-//   V_packed [B,KVH][8 hd-group][T32/32 tile][64 lane][8]  lane=((pos&31)>>3)*16 + (hd&15)
+// cache as coalesced v_mfma_f32_16x16x32_bf16 B-fragments), per (b, kv-head)
+// in the kfrag_off / vfrag_off layouts:
+//   K_packed [B,KVH][T32/16 tile][4 hd-chunk][64 lane][8]
+//   V_packed [B,KVH][8 hd-group][T32/32 tile][64 lane][8]
 // Optional qwen3 per-head q/k RMSNorm (qn/kn weights [hd], fused before the
-// rotation): the slot's wave reduces sum-of-squares over the head row with
-// shfl_xor, then scales while rotating.
+// rotation): the slot's wave reduces sum-of-squares over the head row, then
+// scales while rotating.
 // fp8 packed mode (kp8 non-null): the packed copies are OCP e4m3 bytes with
 // per-row scales sk/sv [B*KVH*T32] — half the decode stream and ~60% of the
 // dual-cache residency (plain cache stays bf16 for prefill). XOT_FP8_KV=1.
+
+// this lane's rotated pair (dims lane, lane + hd/2) of one q or k head row,
+// after the optional per-head RMSNorm (w non-null); lanes >= hd/2 get 0
+DEVINL void rope_head_pair(const unsigned short* row, const unsigned short* __restrict__ w,
+                           const float* __restrict__ cosb, const float* __restrict__ sinb,
+                           int pos, int hd, int lane, float eps, float& f1, float& f2) {
+  const int hd2 = hd >> 1;
+  const bool on = lane < hd2;
+  float x1 = 0.f, x2 = 0.f;
+  if (on) {
+    x1 = b2f(row[lane]);
+    x2 = b2f(row[lane + hd2]);
+  }
+  if (w) {
+    const float inv = rsqrtf(wave_sum(x1 * x1 + x2 * x2) / (float)hd + eps);
+    if (on) {
+      x1 *= inv * b2f(w[lane]);
+      x2 *= inv * b2f(w[lane + hd2]);
+    }
+  }
+  rope_pair(x1, x2, on ? cosb[(size_t)pos * hd2 + lane] : 0.f,
+            on ? sinb[(size_t)pos * hd2 + lane] : 0.f, f1, f2);
+}
+
 __global__ __launch_bounds__(256) void rope_qkv_append_kernel(
     unsigned short* __restrict__ qkv, const float* __restrict__ cosb,
     const float* __restrict__ sinb, const int* __restrict__ positions,
@@ -153,123 +250,61 @@ __global__ __launch_bounds__(256) void rope_qkv_append_kernel(
   if (wid >= B * S * slots) return;
   const int slot = wid % slots;
   const int bs = wid / slots;
-  const int s = bs % S;
   const int b = bs / S;
-  // positions: [S] (shared across batch) or [B*S] (per-row — continuous
-  // batching where every slot decodes at its own position)
-  const int pos = positions[(npos == B * S && npos != S) ? bs : s];
+  const int pos = row_position(positions, npos, B, S, bs);
   const int hd2 = hd >> 1;
   unsigned short* row = qkv + ((size_t)bs * slots + slot) * hd;
   if (slot < H) {
-    float x1 = 0.f, x2 = 0.f;
+    float f1, f2;
+    rope_head_pair(row, qn, cosb, sinb, pos, hd, lane, norm_eps, f1, f2);
     if (lane < hd2) {
-      x1 = b2f(row[lane]);
-      x2 = b2f(row[lane + hd2]);
-    }
-    if (qn) {
-      float ss = x1 * x1 + x2 * x2;
-#pragma unroll
-      for (int m = 32; m > 0; m >>= 1) ss += __shfl_xor(ss, m);
-      const float inv = rsqrtf(ss / (float)hd + norm_eps);
-      if (lane < hd2) {
-        x1 *= inv * b2f(qn[lane]);
-        x2 *= inv * b2f(qn[lane + hd2]);
-      }
-    }
-    if (lane < hd2) {
-      const float c = cosb[(size_t)pos * hd2 + lane];
-      const float sn = sinb[(size_t)pos * hd2 + lane];
-      row[lane] = f2b(x1 * c - x2 * sn);
-      row[lane + hd2] = f2b(x2 * c + x1 * sn);
+      row[lane] = f2b(f1);
+      row[lane + hd2] = f2b(f2);
     }
   } else if (slot < H + KVH) {
-    const int h = slot - H;
-    unsigned short* dst = kc + (((size_t)(b * KVH + h) * T + pos) * hd);
-    float kx1 = 0.f, kx2 = 0.f;
+    const size_t head = (size_t)(b * KVH + (slot - H));
+    float f1, f2;
+    rope_head_pair(row, kn, cosb, sinb, pos, hd, lane, norm_eps, f1, f2);
+    const size_t ktile = (head * (T32 >> 4) + (pos >> 4)) * GQA_KTILE;
+    const size_t o1 = ktile + kfrag_off(lane, pos), o2 = ktile + kfrag_off(lane + hd2, pos);
     if (lane < hd2) {
-      kx1 = b2f(row[lane]);
-      kx2 = b2f(row[lane + hd2]);
-    }
-    if (kn) {
-      float ss = kx1 * kx1 + kx2 * kx2;
-#pragma unroll
-      for (int m = 32; m > 0; m >>= 1) ss += __shfl_xor(ss, m);
-      const float inv = rsqrtf(ss / (float)hd + norm_eps);
-      if (lane < hd2) {
-        kx1 *= inv * b2f(kn[lane]);
-        kx2 *= inv * b2f(kn[lane + hd2]);
-      }
-    }
-    float f1 = 0.f, f2v = 0.f;
-    {
-      const float c = (lane < hd2) ? cosb[(size_t)pos * hd2 + lane] : 0.f;
-      const float sn = (lane < hd2) ? sinb[(size_t)pos * hd2 + lane] : 0.f;
-      f1 = kx1 * c - kx2 * sn;
-      f2v = kx2 * c + kx1 * sn;
-    }
-    if (lane < hd2) {
+      unsigned short* dst = kc + (head * T + pos) * hd;
       dst[lane] = f2b(f1);
-      dst[lane + hd2] = f2b(f2v);
+      dst[lane + hd2] = f2b(f2);
       if (kpc) {
-        // packed K: element for hd-dim d at
-        //   [(b*KVH+h)][pos>>4][d>>5][((d&31)>>3)*16 + (pos&15)][d&7]
-        const size_t base = ((size_t)(b * KVH + h) * (T32 >> 4) + (pos >> 4)) * 2048;
-        const int d1 = lane, d2 = lane + hd2;
-        kpc[base + (size_t)(d1 >> 5) * 512 + (((d1 & 31) >> 3) * 16 + (pos & 15)) * 8 + (d1 & 7)] = f2b(f1);
-        kpc[base + (size_t)(d2 >> 5) * 512 + (((d2 & 31) >> 3) * 16 + (pos & 15)) * 8 + (d2 & 7)] = f2b(f2v);
+        kpc[o1] = f2b(f1);
+        kpc[o2] = f2b(f2);
       }
     }
     if (kp8) {
-      float mx = fmaxf(fabsf(f1), fabsf(f2v));
-#pragma unroll
-      for (int m = 32; m > 0; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
-      const float scl = fmaxf(mx, 1e-12f) / 448.f;
+      const float scl = e4m3_scale(wave_max(fmaxf(fabsf(f1), fabsf(f2))));
       const float inv = 1.f / scl;
-      if (lane == 0) sk[(size_t)(b * KVH + h) * T32 + pos] = scl;
+      if (lane == 0) sk[head * T32 + pos] = scl;
       if (lane < hd2) {
-        const size_t base = ((size_t)(b * KVH + h) * (T32 >> 4) + (pos >> 4)) * 2048;
-        const int d1 = lane, d2 = lane + hd2;
-        const unsigned short p1 = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(f1 * inv, 0.f, 0, false);
-        const unsigned short p2 = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(f2v * inv, 0.f, 0, false);
-        kp8[base + (size_t)(d1 >> 5) * 512 + (((d1 & 31) >> 3) * 16 + (pos & 15)) * 8 + (d1 & 7)] = (unsigned char)(p1 & 0xff);
-        kp8[base + (size_t)(d2 >> 5) * 512 + (((d2 & 31) >> 3) * 16 + (pos & 15)) * 8 + (d2 & 7)] = (unsigned char)(p2 & 0xff);
+        kp8[o1] = to_e4m3(f1 * inv);
+        kp8[o2] = to_e4m3(f2 * inv);
       }
     }
   } else {
-    const int h = slot - H - KVH;
-    unsigned short* dst = vc + (((size_t)(b * KVH + h) * T + pos) * hd);
-    if (lane * 2 < hd)
-      *(unsigned int*)(dst + lane * 2) = *(const unsigned int*)(row + lane * 2);
-    if (vpc && lane * 2 < hd) {
-      // packed V: element for hd-dim d at
-      //   [(b*KVH+h)][d>>4][pos>>5][((pos&31)>>3)*16 + (d&15)][pos&7]
-      const int tp = pos >> 5, qt = (pos & 31) >> 3, j = pos & 7;
-      const size_t gbase = (size_t)(b * KVH + h) * 8;
+    const size_t head = (size_t)(b * KVH + (slot - H - KVH));
+    unsigned short* dst = vc + (head * T + pos) * hd;
+    const bool on = lane * 2 < hd;
+    if (on) *(unsigned int*)(dst + lane * 2) = *(const unsigned int*)(row + lane * 2);
+    const size_t vhead = head * GQA_VGROUPS * (T32 >> 5) * FRAG;
+    if (vpc && on) {
 #pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int d = lane * 2 + e;
-        vpc[((gbase + (d >> 4)) * (T32 >> 5) + tp) * 512 + (qt * 16 + (d & 15)) * 8 + j] = row[d];
-      }
+      for (int e = 0; e < 2; ++e) vpc[vhead + vfrag_off(lane * 2 + e, pos, T32 >> 5)] = row[lane * 2 + e];
     }
     if (vp8) {
       float mx = 0.f;
-      if (lane * 2 < hd) {
-        mx = fmaxf(fabsf(b2f(row[lane * 2])), fabsf(b2f(row[lane * 2 + 1])));
-      }
-#pragma unroll
-      for (int m = 32; m > 0; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
-      const float scl = fmaxf(mx, 1e-12f) / 448.f;
+      if (on) mx = fmaxf(fabsf(b2f(row[lane * 2])), fabsf(b2f(row[lane * 2 + 1])));
+      const float scl = e4m3_scale(wave_max(mx));
       const float inv = 1.f / scl;
-      if (lane == 0) sv[(size_t)(b * KVH + h) * T32 + pos] = scl;
-      if (lane * 2 < hd) {
-        const int tp = pos >> 5, qt = (pos & 31) >> 3, j = pos & 7;
-        const size_t gbase = (size_t)(b * KVH + h) * 8;
+      if (lane == 0) sv[head * T32 + pos] = scl;
+      if (on) {
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const int d = lane * 2 + e;
-          const unsigned short pk = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(b2f(row[d]) * inv, 0.f, 0, false);
-          vp8[((gbase + (d >> 4)) * (T32 >> 5) + tp) * 512 + (qt * 16 + (d & 15)) * 8 + j] = (unsigned char)(pk & 0xff);
-        }
+        for (int e = 0; e < 2; ++e)
+          vp8[vhead + vfrag_off(lane * 2 + e, pos, T32 >> 5)] = to_e4m3(b2f(row[lane * 2 + e]) * inv);
       }
     }
   }
@@ -286,6 +321,31 @@ __global__ __launch_bounds__(256) void rope_qkv_append_kernel(
 // (group, head); group partials merged through LDS; one (m, l, o[hd]) fp32
 // partial per (b, qh, split) written to the workspace.
 // ---------------------------------------------------------------------------
+
+// merge of the split-KV partials (VALU, MFMA and MLA decode): one workgroup
+// per (b, head), 128 threads (256 at HD = 512), HD / threads dims per thread
+template <int HD>
+__global__ __launch_bounds__(HD > 128 ? 256 : 128) void attn_decode_merge(
+    const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
+    unsigned short* __restrict__ out, int nsplit) {
+  constexpr int NT = HD > 128 ? 256 : 128;
+  const int bh = blockIdx.x;  // b * H + qh
+  if (HD <= NT && threadIdx.x >= HD) return;
+  float M = -INFINITY;
+  for (int i = 0; i < nsplit; ++i) M = fmaxf(M, ws_ml[((size_t)bh * nsplit + i) * 2 + 0]);
+#pragma unroll
+  for (int e = 0; e < (HD + NT - 1) / NT; ++e) {
+    const int d = threadIdx.x + e * NT;
+    float L = 0.f, O = 0.f;
+    for (int i = 0; i < nsplit; ++i) {
+      const float lg = ws_ml[((size_t)bh * nsplit + i) * 2 + 1];
+      const float alpha = (lg > 0.f) ? __expf(ws_ml[((size_t)bh * nsplit + i) * 2 + 0] - M) : 0.f;
+      L += alpha * lg;
+      O += alpha * ws_o[((size_t)bh * nsplit + i) * HD + d];
+    }
+    out[(size_t)bh * HD + d] = f2b(L > 0.f ? O / L : 0.f);
+  }
+}
 
 template <int NQ, int HD>
 __global__ __launch_bounds__(256) void attn_decode_partial(
@@ -426,6 +486,141 @@ __global__ __launch_bounds__(256) void attn_decode_partial(
 // the VALU split-KV kernel above stays as the hd=64 / unpacked-cache path.
 // ---------------------------------------------------------------------------
 
+// MFMA operand fragment of the packed cache, keyed on the fp8 mode: register
+// type, element type of the stream it is loaded from, and the 16x16x32 MFMA
+template <bool FP8>
+struct Frag {
+  using T = bf16x8;
+  using E = unsigned short;
+  static DEVINL floatx4 mfma(T a, T b, floatx4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+};
+
+template <>
+struct Frag<true> {
+  using T = long;
+  using E = unsigned char;
+  static DEVINL floatx4 mfma(T a, T b, floatx4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0);
+  }
+};
+
+template <bool FP8>
+DEVINL typename Frag<FP8>::T frag_load(const typename Frag<FP8>::E* p) {
+  return *reinterpret_cast<const typename Frag<FP8>::T*>(p);
+}
+
+template <bool FP8>
+DEVINL typename Frag<FP8>::T frag_load_nt(const typename Frag<FP8>::E* p) {
+  return __builtin_nontemporal_load(reinterpret_cast<const typename Frag<FP8>::T*>(p));
+}
+
+// The online-softmax step over one 32-position tile of the GQA decode kernel.
+// In: sc0, sc1 = the two masked, scaled 16-column half-tiles of scores (this
+// lane's 4 rows r, its column lane & 15). Out: p in sc0 / sc1, updated running
+// max m and sum lsum, and alpha = the rescale of everything accumulated before
+// this tile. Every decode tile has a visible position, so no row is all -inf.
+// The prefill and MLA kernels keep their own copy of these lines (prefill
+// with its all-masked-row guard): called through this helper, LLVM promotes
+// the by-reference arrays as vectors and schedules their main loops
+// differently, which measured 1-2% slower there.
+DEVINL void attn_softmax_tile(floatx4& sc0, floatx4& sc1, float (&m)[4], float (&lsum)[4], float (&alpha)[4]) {
+  float rmax[4], rsum[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(sc0[r], sc1[r]);
+#pragma unroll
+  for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(rmax[r], __shfl_xor(rmax[r], mm));
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float mn = fmaxf(m[r], rmax[r]);
+    alpha[r] = (lsum[r] > 0.f) ? __expf(m[r] - mn) : 0.f;
+    m[r] = mn;
+    const float p0 = __expf(sc0[r] - mn);
+    const float p1 = __expf(sc1[r] - mn);
+    sc0[r] = p0;
+    sc1[r] = p1;
+    rsum[r] = p0 + p1;
+  }
+#pragma unroll
+  for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rsum[r] += __shfl_xor(rsum[r], mm);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) lsum[r] = lsum[r] * alpha[r] + rsum[r];
+}
+
+// acco (NG 16-dim output groups) *= alpha[row] * f
+template <int NG>
+DEVINL void attn_rescale(floatx4 (&acco)[NG], const float (&alpha)[4], float f) {
+#pragma unroll
+  for (int g = 0; g < NG; ++g)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acco[g][r] *= alpha[r] * f;
+}
+
+// fp8 PV running scale: s_pv = the tile's V-scale ceiling; acco is kept in
+// units of 1/R so the quantized P' = p * s_v[pos] / s_pv enters at full e4m3
+// range. vs = this head's per-position V scales. Returns s_pv, sets rfac (the
+// factor that moves acco from the old R to the new) and R.
+DEVINL float attn_fp8_pv_scale(const float* __restrict__ vs, int t, int T32, int lane, float& R, float& rfac) {
+  const float s_pv = fmaxf(wave_max(vs[min(t + (lane & 31), T32 - 1)]), 1e-12f);
+  rfac = R / s_pv;
+  R = s_pv;
+  return s_pv;
+}
+
+// P -> LDS image (16 rows x 32 positions, 48-element row stride: 96 B for
+// bf16, conflict-free b128 reads) and back as the PV MFMA's A fragment
+// [row = lane & 15][k = (lane >> 4) * 8 + j]. FP8 stores p * s_v[pos] / s_pv
+// as e4m3 bytes (vs / s_pv as in attn_fp8_pv_scale; unused otherwise).
+// GQA decode kernel only: the prefill and MLA kernels store through their own
+// LDS pointer — passed through a parameter, LLVM resolves the LDS address
+// space later and their loops came out 1-26% slower.
+template <bool FP8>
+DEVINL typename Frag<FP8>::T attn_p_fragment(unsigned short* plds, const floatx4 (&sc)[2], int lane,
+                                             const float* __restrict__ vs, int t, int T32, float s_pv) {
+  typename Frag<FP8>::E* pl = reinterpret_cast<typename Frag<FP8>::E*>(plds);
+  const int col = lane & 15;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    float svv = 1.f;
+    if constexpr (FP8) svv = vs[min(t + h * 16 + col, T32 - 1)];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = ((lane >> 4) * 4 + r) * 48 + h * 16 + col;
+      if constexpr (FP8) pl[i] = to_e4m3(sc[h][r] * svv / s_pv);
+      else pl[i] = f2b(sc[h][r]);
+    }
+  }
+  return frag_load<FP8>(pl + col * 48 + (lane >> 4) * 8);
+}
+
+// split-KV epilogue: the wave's 16 query rows (nq of them real, heads
+// bh0 .. bh0 + nq - 1 with bh = b * H + head) each store one fp32
+// (m, l, o[NG * 16]) partial for this split; oscale undoes the fp8 R units.
+template <int NG>
+DEVINL void attn_store_partial(float* __restrict__ ws_o, float* __restrict__ ws_ml,
+                               const floatx4 (&acco)[NG], const float (&m)[4], const float (&lsum)[4],
+                               int lane, int nq, int bh0, int nsplit, int split, float oscale) {
+  const int col = lane & 15;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int qrow = (lane >> 4) * 4 + r;
+    if (qrow < nq) {
+      const size_t pidx = ((size_t)(bh0 + qrow) * nsplit + split);
+#pragma unroll
+      for (int g = 0; g < NG; ++g) ws_o[pidx * (NG * 16) + g * 16 + col] = acco[g][r] * oscale;
+      if (col == 0) {
+        ws_ml[pidx * 2 + 0] = m[r];
+        ws_ml[pidx * 2 + 1] = lsum[r];
+      }
+    }
+  }
+}
+
 // softcap > 0 applies gemma2's attention-logit soft-capping
 // (s = cap * tanh(s / cap), after scale, before masking); window > 0 is the
 // sliding-window mask (query at sl-1 sees positions [sl - window, sl)).
@@ -458,112 +653,87 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
   const int c1 = min(split * chunk + chunk, sl);
   unsigned short* plds = plds_all[wv];
 
+  using F = Frag<FP8>;
+  using FT = typename F::T;
+  using FE = typename F::E;
+
   // Q fragments: A[i = lane&15 (query head, clamped), k = (lane>>4)*8 + j]
   const int qh_base = kvh * NQ;
   const int qi = min(lane & 15, NQ - 1);
-  bf16x8 qf[4];
-  {
-    const unsigned short* qrow = q + (size_t)b * q_stride + (size_t)(qh_base + qi) * 128;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      qf[c] = *reinterpret_cast<const bf16x8*>(qrow + c * 32 + (lane >> 4) * 8);
-  }
-  long qf8[4];
+  FT qf[4];
   float srow[4];
-  if (FP8) {
-    float mx = 0.f;
+  {
+    const unsigned short* qrow = q + (size_t)b * q_stride + (size_t)(qh_base + qi) * 128 + (lane >> 4) * 8;
+    bf16x8 qb[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
+    for (int c = 0; c < 4; ++c) qb[c] = frag_load<false>(qrow + c * 32);
+    if constexpr (FP8) {
+      // quantize per head: amax over the 4 lanes x 32 elements of the row
+      float mx = 0.f;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf((float)qf[c][j]));
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float sq = fmaxf(mx, 1e-12f) / 448.f;
-    const float inv = 1.f / sq;
+      for (int c = 0; c < 4; ++c)
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      unsigned char o[8];
+        for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf((float)qb[c][j]));
+      mx = fmaxf(mx, __shfl_xor(mx, 16));
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float sq = e4m3_scale(mx);
+      const float inv = 1.f / sq;
 #pragma unroll
-      for (int j = 0; j < 8; j += 2) {
-        const unsigned short pk = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(
-            (float)qf[c][j] * inv, (float)qf[c][j + 1] * inv, 0, false);
-        o[j] = (unsigned char)(pk & 0xff);
-        o[j + 1] = (unsigned char)(pk >> 8);
-      }
-      qf8[c] = *reinterpret_cast<const long*>(o);
+      for (int c = 0; c < 4; ++c) qf[c] = to_e4m3x8(qb[c], inv);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) srow[r] = __shfl(sq, (lane >> 4) * 4 + r);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) qf[c] = qb[c];
     }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) srow[r] = __shfl(sq, (lane >> 4) * 4 + r);
   }
 
-  float m[4], lsum[4];
-  floatx4 acco[8];
+  float m[4], lsum[4], Rscale = 1.f;
+  floatx4 acco[GQA_VGROUPS];
 #pragma unroll
   for (int r = 0; r < 4; ++r) { m[r] = -INFINITY; lsum[r] = 0.f; }
 #pragma unroll
-  for (int g = 0; g < 8; ++g) acco[g] = (floatx4)(0.f);
+  for (int g = 0; g < GQA_VGROUPS; ++g) acco[g] = (floatx4)(0.f);
 
-  const size_t kbase = (size_t)(b * KVH + kvh) * (T32 >> 4) * 2048;
-  const size_t vbase = (size_t)(b * KVH + kvh) * 8 * (T32 >> 5) * 512;
+  // this (b, kv-head)'s K / V images at this lane's slice of every fragment,
+  // and (fp8) its per-position scale rows
+  const size_t head = (size_t)(b * KVH + kvh);
+  const FE* khead = reinterpret_cast<const FE*>(kp) + head * (T32 >> 4) * GQA_KTILE + lane * 8;
+  const FE* vhead = reinterpret_cast<const FE*>(vp) + head * GQA_VGROUPS * (T32 >> 5) * FRAG + lane * 8;
+  const float* ks_row = FP8 ? sk + head * T32 : nullptr;
+  const float* vs_row = FP8 ? sv + head * T32 : nullptr;
   const int col = lane & 15;
 
-  // PREFETCH: the next tile's 8 K fragments are loaded during the previous
-  // tile's PV phase (kbuf registers, +32 VGPR) so the score MFMAs never
-  // wait on HBM; measured A/B via XOT_ATTN_PREFETCH.
-  bf16x8 kbuf[8];
-  long kbuf8[8];
-  const unsigned char* kp8 = reinterpret_cast<const unsigned char*>(kp);
-  const unsigned char* vp8 = reinterpret_cast<const unsigned char*>(vp);
-  const size_t ssbase = (size_t)(b * KVH + kvh) * T32;
-  float Rscale = 1.f;
-  if (PREFETCH && c0 < c1) {
+  // the 8 K fragments (2 half-tiles x 4 hd-chunks) of the 32-position tile at t.
+  // PREFETCH: the next tile's are loaded during the previous tile's PV phase
+  // (kbuf stays live, +32 VGPR) so the score MFMAs never wait on HBM;
+  // measured A/B via XOT_ATTN_PREFETCH.
+  FT kbuf[8];
+  auto load_k_tile = [&](int t) {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      if (FP8) {
-        const unsigned char* kt = kp8 + kbase + ((size_t)((c0 >> 4) + h)) * 2048 + (size_t)lane * 8;
+    for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
-          kbuf8[h * 4 + c] = __builtin_nontemporal_load(reinterpret_cast<const long*>(kt + c * 512));
-      } else {
-        const unsigned short* kt = kp + kbase + ((size_t)((c0 >> 4) + h)) * 2048 + (size_t)lane * 8;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          kbuf[h * 4 + c] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kt + c * 512));
-      }
-    }
-  }
+      for (int c = 0; c < 4; ++c)
+        kbuf[h * 4 + c] = frag_load_nt<FP8>(khead + (size_t)((t >> 4) + h) * GQA_KTILE + c * FRAG);
+  };
+  if (PREFETCH && c0 < c1) load_k_tile(c0);
 
   for (int t = c0; t < c1; t += 32) {
     // ---- scores: two 16-position half-tiles ----
+    if (!PREFETCH) load_k_tile(t);
     floatx4 sc[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       sc[h] = (floatx4)(0.f);
-      if (FP8) {
-        const unsigned char* kt = kp8 + kbase + ((size_t)((t >> 4) + h)) * 2048 + (size_t)lane * 8;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const long kb = PREFETCH ? kbuf8[h * 4 + c]
-              : __builtin_nontemporal_load(reinterpret_cast<const long*>(kt + c * 512));
-          sc[h] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(qf8[c], kb, sc[h], 0, 0, 0);
-        }
-      } else {
-        const unsigned short* kt = kp + kbase + ((size_t)((t >> 4) + h)) * 2048 + (size_t)lane * 8;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const bf16x8 kb = PREFETCH ? kbuf[h * 4 + c]
-              : __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kt + c * 512));
-          sc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[c], kb, sc[h], 0, 0, 0);
-        }
-      }
+      for (int c = 0; c < 4; ++c) sc[h] = F::mfma(qf[c], kbuf[h * 4 + c], sc[h]);
     }
-    // ---- online softmax (rows r are this lane's 4 query heads) ----
-    float rmax[4];
+    // ---- scale, softcap, mask (rows r are this lane's 4 query heads) ----
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int pos = t + h * 16 + col;
       const bool ok = pos < c1 && pos >= win_lo;
-      const float skc = FP8 ? sk[ssbase + min(pos, T32 - 1)] : 1.f;
+      const float skc = FP8 ? ks_row[min(pos, T32 - 1)] : 1.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float s = sc[h][r] * scale;
@@ -572,121 +742,23 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
         sc[h][r] = ok ? s : -INFINITY;
       }
     }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(sc[0][r], sc[1][r]);
-#pragma unroll
-    for (int mm = 1; mm < 16; mm <<= 1)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(rmax[r], __shfl_xor(rmax[r], mm));
-    float alpha[4], rsum[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float mn = fmaxf(m[r], rmax[r]);
-      alpha[r] = (lsum[r] > 0.f) ? __expf(m[r] - mn) : 0.f;
-      m[r] = mn;
-      float p0 = __expf(sc[0][r] - mn);
-      float p1 = __expf(sc[1][r] - mn);
-      sc[0][r] = p0;
-      sc[1][r] = p1;
-      rsum[r] = p0 + p1;
-    }
-#pragma unroll
-    for (int mm = 1; mm < 16; mm <<= 1)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) rsum[r] += __shfl_xor(rsum[r], mm);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) lsum[r] = lsum[r] * alpha[r] + rsum[r];
-    float s_pv = 1.f, rfac = 1.f;
-    if (FP8) {
-      // per-tile V scale ceiling; acco is kept in units of 1/R so quantized
-      // P' = p * s_v[pos] / s_pv enters at full e4m3 range
-      float mv = sv[ssbase + min(t + (lane & 31), T32 - 1)];
-#pragma unroll
-      for (int m_ = 32; m_ > 0; m_ >>= 1) mv = fmaxf(mv, __shfl_xor(mv, m_));
-      s_pv = fmaxf(mv, 1e-12f);
-      rfac = Rscale / s_pv;
-      Rscale = s_pv;
-    }
-#pragma unroll
-    for (int g = 0; g < 8; ++g)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acco[g][r] *= alpha[r] * (FP8 ? rfac : 1.f);
-    // ---- P -> LDS (bf16 / fp8 bytes, conflict-padded) and back as A fragments ----
-    long pf8 = 0;
-    bf16x8 pf;
-    if (FP8) {
-      unsigned char* pl8 = reinterpret_cast<unsigned char*>(plds);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int pos = t + h * 16 + col;
-        const float svv = sv[ssbase + min(pos, T32 - 1)];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const unsigned short pk = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(
-              sc[h][r] * svv / s_pv, 0.f, 0, false);
-          pl8[((lane >> 4) * 4 + r) * 48 + h * 16 + col] = (unsigned char)(pk & 0xff);
-        }
-      }
-      pf8 = *reinterpret_cast<const long*>(pl8 + (lane & 15) * 48 + (lane >> 4) * 8);
-    } else {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          plds[((lane >> 4) * 4 + r) * 48 + h * 16 + col] = f2b(sc[h][r]);
-      pf = *reinterpret_cast<const bf16x8*>(plds + (lane & 15) * 48 + (lane >> 4) * 8);
-    }
-    if (PREFETCH && t + 32 < c1) {
-      // issue next tile's K stream now; it completes under the PV MFMAs
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        if (FP8) {
-          const unsigned char* kt = kp8 + kbase + ((size_t)(((t + 32) >> 4) + h)) * 2048 + (size_t)lane * 8;
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            kbuf8[h * 4 + c] = __builtin_nontemporal_load(reinterpret_cast<const long*>(kt + c * 512));
-        } else {
-          const unsigned short* kt = kp + kbase + ((size_t)(((t + 32) >> 4) + h)) * 2048 + (size_t)lane * 8;
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            kbuf[h * 4 + c] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kt + c * 512));
-        }
-      }
-    }
+    float alpha[4], s_pv = 1.f, rfac = 1.f;
+    attn_softmax_tile(sc[0], sc[1], m, lsum, alpha);
+    if (FP8) s_pv = attn_fp8_pv_scale(vs_row, t, T32, lane, Rscale, rfac);
+    attn_rescale(acco, alpha, rfac);
+    const FT pf = attn_p_fragment<FP8>(plds, sc, lane, vs_row, t, T32, s_pv);
+    // issue next tile's K stream now; it completes under the PV MFMAs
+    if (PREFETCH && t + 32 < c1) load_k_tile(t + 32);
     // ---- PV: out[16q][g*16..] += P x V ----
-    if (FP8) {
-      const unsigned char* vt = vp8 + vbase + (size_t)(t >> 5) * 512 + (size_t)lane * 8;
+    const FE* vt = vhead + (size_t)(t >> 5) * FRAG;
 #pragma unroll
-      for (int g = 0; g < 8; ++g) {
-        const long vb = __builtin_nontemporal_load(
-            reinterpret_cast<const long*>(vt + (size_t)g * (T32 >> 5) * 512));
-        acco[g] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pf8, vb, acco[g], 0, 0, 0);
-      }
-    } else {
-      const unsigned short* vt = vp + vbase + (size_t)(t >> 5) * 512 + (size_t)lane * 8;
-#pragma unroll
-      for (int g = 0; g < 8; ++g) {
-        const bf16x8 vb = __builtin_nontemporal_load(
-            reinterpret_cast<const bf16x8*>(vt + (size_t)g * (T32 >> 5) * 512));
-        acco[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vb, acco[g], 0, 0, 0);
-      }
-    }
+    for (int g = 0; g < GQA_VGROUPS; ++g)
+      acco[g] = F::mfma(pf, frag_load_nt<FP8>(vt + (size_t)g * (T32 >> 5) * FRAG), acco[g]);
   }
 
   // ---- epilogue: one (m, l, o[128]) partial per (b, qh, split) ----
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int qrow = (lane >> 4) * 4 + r;
-    if (qrow < NQ) {
-      const size_t pidx = ((size_t)(b * H + qh_base + qrow) * nsplit + split);
-#pragma unroll
-      for (int g = 0; g < 8; ++g) ws_o[pidx * 128 + g * 16 + col] = acco[g][r] * (FP8 ? Rscale : 1.f);
-      if (col == 0) {
-        ws_ml[pidx * 2 + 0] = m[r];
-        ws_ml[pidx * 2 + 1] = lsum[r];
-      }
-    }
-  }
+  attn_store_partial(ws_o, ws_ml, acco, m, lsum, lane, NQ, b * H + qh_base, nsplit, split,
+                     FP8 ? Rscale : 1.f);
 }
 
 // ---------------------------------------------------------------------------
@@ -723,7 +795,8 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
   const int r0 = qb * 128 + wv * 32;
   const int col = lane & 15;
 
-  __shared__ unsigned short kv_lds[2][8192];  // K tile 8 KB + V tile 8 KB, dbuf
+  constexpr int KV_K = 2 * GQA_KTILE, KV_V = GQA_VGROUPS * FRAG;
+  __shared__ unsigned short kv_lds[2][KV_K + KV_V];  // dbuf
 
   // Q fragments for 2 sub-tiles x 4 hd-chunks; rows clamped to S-1 (writes
   // are predicated, extra rows only waste compute)
@@ -734,11 +807,11 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
     const unsigned short* qrow = q + (size_t)b * q_bstride + (size_t)row * q_sstride + (size_t)h * 128;
 #pragma unroll
     for (int c = 0; c < 4; ++c)
-      qf[t][c] = *reinterpret_cast<const bf16x8*>(qrow + c * 32 + (lane >> 4) * 8);
+      qf[t][c] = frag_load<false>(qrow + c * 32 + (lane >> 4) * 8);
   }
 
   float m[2][4], lsum[2][4];
-  floatx4 acco[2][8];
+  floatx4 acco[2][GQA_VGROUPS];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -748,8 +821,8 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
 #pragma unroll
     for (int g = 0; g < 8; ++g) acco[t][g] = (floatx4)(0.f);
 
-  const size_t kbase = (size_t)(b * KVH + kvh) * (T32 >> 4) * 2048;
-  const size_t vbase = (size_t)(b * KVH + kvh) * 8 * (T32 >> 5) * 512;
+  const size_t kbase = (size_t)(b * KVH + kvh) * (T32 >> 4) * GQA_KTILE;
+  const size_t vbase = (size_t)(b * KVH + kvh) * GQA_VGROUPS * (T32 >> 5) * FRAG;
   // causal end for the BLOCK (max row): positions [0, start_pos + block_hi]
   const int block_hi = min(qb * 128 + 127, S - 1);
   const int kv_end = start_pos + block_hi + 1;  // exclusive
@@ -760,10 +833,10 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
   auto stage = [&](int tp, int buf) {
     // K: two 16-pos tiles x 4 chunks x 512 elems; V: 8 groups x 512 elems
     // 256 threads x 24 pieces of 256 B... simpler: each thread copies 16 B x3
-    const unsigned short* ksrc = kp + kbase + (size_t)(tp * 2) * 2048;
-    const unsigned short* vsrc = vp + vbase + (size_t)tp * 512;
+    const unsigned short* ksrc = kp + kbase + (size_t)(tp * 2) * GQA_KTILE;
+    const unsigned short* vsrc = vp + vbase + (size_t)tp * FRAG;
     unsigned short* dk = kv_lds[buf];
-    unsigned short* dv = kv_lds[buf] + 4096;
+    unsigned short* dv = kv_lds[buf] + KV_K;
     const int tid = threadIdx.x;
     // K: 4096 elems = 8192 B: 256 threads x 2 x 16 B
 #pragma unroll
@@ -776,8 +849,8 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
     for (int i = 0; i < 2; ++i) {
       const int e = tid + i * 256;           // 0..511 -> (group, piece)
       const int g = e >> 6, piece = e & 63;  // 64 pieces of 8 elems per group
-      *(ushort8*)(dv + g * 512 + piece * 8) =
-          *(const ushort8*)(vsrc + (size_t)g * (T32 >> 5) * 512 + piece * 8);
+      *(ushort8*)(dv + g * FRAG + piece * 8) =
+          *(const ushort8*)(vsrc + (size_t)g * (T32 >> 5) * FRAG + piece * 8);
     }
   };
 
@@ -792,7 +865,7 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
     const int buf = tp & 1;
     if (tp + 1 < ntiles) stage(tp + 1, buf ^ 1);  // plain loads overlap compute
     const unsigned short* dk = kv_lds[buf];
-    const unsigned short* dv = kv_lds[buf] + 4096;
+    const unsigned short* dv = kv_lds[buf] + KV_K;
     unsigned short* plds = plds_all[wv];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -803,8 +876,8 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
         sc[hh] = (floatx4)(0.f);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const bf16x8 kb = *reinterpret_cast<const bf16x8*>(dk + (hh * 4 + c) * 512 + lane * 8);
-          sc[hh] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[t][c], kb, sc[hh], 0, 0, 0);
+          const bf16x8 kb = *reinterpret_cast<const bf16x8*>(dk + (hh * 4 + c) * FRAG + lane * 8);
+          sc[hh] = Frag<false>::mfma(qf[t][c], kb, sc[hh]);
         }
       }
       // causal mask: kv pos must be < start_pos + row + 1
@@ -847,10 +920,7 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
         for (int r = 0; r < 4; ++r) rsum[r] += __shfl_xor(rsum[r], mm);
 #pragma unroll
       for (int r = 0; r < 4; ++r) lsum[t][r] = lsum[t][r] * alpha[r] + rsum[r];
-#pragma unroll
-      for (int g = 0; g < 8; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acco[t][g][r] *= alpha[r];
+      attn_rescale(acco[t], alpha, 1.f);
       unsigned short* pl = plds + t * 16 * 48;  // reuse the 2x buffer per sub-tile
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh)
@@ -860,8 +930,8 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
       const bf16x8 pf = *reinterpret_cast<const bf16x8*>(pl + (lane & 15) * 48 + (lane >> 4) * 8);
 #pragma unroll
       for (int g = 0; g < 8; ++g) {
-        const bf16x8 vb = *reinterpret_cast<const bf16x8*>(dv + g * 512 + lane * 8);
-        acco[t][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vb, acco[t][g], 0, 0, 0);
+        const bf16x8 vb = *reinterpret_cast<const bf16x8*>(dv + g * FRAG + lane * 8);
+        acco[t][g] = Frag<false>::mfma(pf, vb, acco[t][g]);
       }
     }
     __syncthreads();  // all waves done with kv_lds[buf] before restaging
@@ -896,25 +966,6 @@ __global__ void mfma16_probe_kernel(const unsigned short* __restrict__ A,
   d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, d, 0, 0, 0);
 #pragma unroll
   for (int r = 0; r < 4; ++r) D[((lane >> 4) * 4 + r) * 16 + (lane & 15)] = d[r];
-}
-
-template <int HD>
-__global__ __launch_bounds__(128) void attn_decode_merge(
-    const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
-    unsigned short* __restrict__ out, int nsplit) {
-  const int bh = blockIdx.x;  // b * H + qh
-  const int d = threadIdx.x;
-  if (d >= HD) return;
-  float M = -INFINITY;
-  for (int i = 0; i < nsplit; ++i) M = fmaxf(M, ws_ml[((size_t)bh * nsplit + i) * 2 + 0]);
-  float L = 0.f, O = 0.f;
-  for (int i = 0; i < nsplit; ++i) {
-    const float lg = ws_ml[((size_t)bh * nsplit + i) * 2 + 1];
-    const float alpha = (lg > 0.f) ? __expf(ws_ml[((size_t)bh * nsplit + i) * 2 + 0] - M) : 0.f;
-    L += alpha * lg;
-    O += alpha * ws_o[((size_t)bh * nsplit + i) * HD + d];
-  }
-  out[(size_t)bh * HD + d] = f2b(L > 0.f ? O / L : 0.f);
 }
 
 // ---------------------------------------------------------------------------
@@ -1125,12 +1176,13 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(
 //   scores[16h][16p]: 18 x v_mfma_f32_16x16x32_bf16 per half-tile
 //     (A = q fragments re-gathered from L1, B = 1 KB coalesced packed-cache
 //      streams — same fragment geometry as the GQA kernel)
-//   online softmax via 4 x shfl over 16-lane column groups (shared code shape)
+//   online softmax via 4 x shfl over 16-lane column groups (same lines as the
+//     GQA kernel's attn_softmax_tile; the rescale and fp8 PV scale are shared)
 //   out_lat[16h][512] += 32 x mfma (P from LDS image, V = packed latent)
 // One wave per (b, head-group, split); fp32 (m, l, o[512]) partials merged
-// by attn_decode_merge512.  Latent+rope cache copies are kept in the SAME
-// fragment-packed layouts as the GQA kp/vp (18 qk-chunks / 32 pv-groups),
-// appended by mla_append_kernel.
+// by attn_decode_merge<512>.  Latent+rope cache copies are kept in the SAME
+// fragment-packed layouts as the GQA kp/vp (kfrag_off / vfrag_off with
+// 18 qk-chunks / 32 pv-groups), appended by mla_append_kernel.
 // ---------------------------------------------------------------------------
 
 #define MLA_LAT 512
@@ -1138,6 +1190,18 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(
 #define MLA_DQK 576   // latent + rope, the absorbed q/k width
 #define MLA_CHQK 18   // 32-dim MFMA chunks across DQK
 #define MLA_GPV 32    // 16-dim output groups across LAT
+#define MLA_KTILE (MLA_CHQK * FRAG)  // one 16-position K tile of the latent+rope image
+
+// rope of a 64-dim MLA tail x: lane l < 32 owns the input pair (2l, 2l+1)
+// (interleaved convention) or (l, l+32) (half); the rotated pair is always
+// output dims (l, l+32) — HALF layout, cat([x1c - x2s, x2c + x1s]) like _rope
+DEVINL void mla_rope_pair(const unsigned short* x, const float* __restrict__ cosb,
+                          const float* __restrict__ sinb, int pos, int lane, int interleave,
+                          float& r1, float& r2) {
+  const int i1 = interleave ? lane * 2 : lane;
+  const int i2 = interleave ? lane * 2 + 1 : lane + 32;
+  rope_pair(b2f(x[i1]), b2f(x[i2]), cosb[(size_t)pos * 32 + lane], sinb[(size_t)pos * 32 + lane], r1, r2);
+}
 
 // Fused MLA KV-side prep: raw kv_a output [B,S,576] -> RMSNorm the 512-dim
 // latent (fp32 math, weight w), rope the 64-dim shared key at `positions`
@@ -1158,9 +1222,8 @@ __global__ __launch_bounds__(256) void mla_prep_append_kernel(
   const int wid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (wid >= B * S) return;
   const int lane = threadIdx.x & 63;
-  const int s = wid % S;
   const int b = wid / S;
-  const int pos = positions[(npos == B * S && npos != S) ? wid : s];
+  const int pos = row_position(positions, npos, B, S, wid);
   const unsigned short* row = ckv + (size_t)wid * MLA_DQK;
   // ---- rms over the 512 latent dims ----
   float v[8];
@@ -1170,48 +1233,35 @@ __global__ __launch_bounds__(256) void mla_prep_append_kernel(
     v[j] = b2f(row[lane * 8 + j]);
     acc += v[j] * v[j];
   }
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m);
-  const float inv = rsqrtf(acc / (float)MLA_LAT + eps);
+  const float inv = rsqrtf(wave_sum(acc) / (float)MLA_LAT + eps);
   float lat[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) lat[j] = v[j] * inv * b2f(w[lane * 8 + j]);
   // ---- rope the 64-dim shared key (lanes 0..31 handle one pair each) ----
   float r1 = 0.f, r2 = 0.f;
-  if (lane < 32) {
-    const float c = cosb[(size_t)pos * 32 + lane];
-    const float sn = sinb[(size_t)pos * 32 + lane];
-    int i1, i2;
-    if (interleave) { i1 = lane * 2; i2 = lane * 2 + 1; }
-    else            { i1 = lane;     i2 = lane + 32;    }
-    const float x1 = b2f(row[MLA_LAT + i1]);
-    const float x2 = b2f(row[MLA_LAT + i2]);
-    // output is cat([x1c - x2s, x2c + x1s]) in HALF layout (matches _rope)
-    r1 = x1 * c - x2 * sn;
-    r2 = x2 * c + x1 * sn;
-  }
+  if (lane < 32) mla_rope_pair(row + MLA_LAT, cosb, sinb, pos, lane, interleave, r1, r2);
   // plain caches (bf16, prefill reader) + bf16 packed copies
   unsigned short* lrow = lat_c + ((size_t)b * T + pos) * MLA_LAT;
   unsigned short* rrow = rot_c + ((size_t)b * T + pos) * MLA_ROPE;
-  const size_t kbase = ((size_t)b * (T32 >> 4) + (pos >> 4)) * MLA_CHQK * 512;
-  const size_t vbase = (size_t)b * MLA_GPV * (T32 >> 5) * 512;
+  const int tiles32 = T32 >> 5;
+  const size_t ktile = ((size_t)b * (T32 >> 4) + (pos >> 4)) * MLA_KTILE;
+  const size_t vhead = (size_t)b * MLA_GPV * tiles32 * FRAG;
+  const int d1 = MLA_LAT + lane, d2 = MLA_LAT + lane + 32;  // the rope pair's k dims
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int d = lane * 8 + j;
     lrow[d] = f2b(lat[j]);
     if (kp) {
-      kp[kbase + (size_t)(d >> 5) * 512 + (((d & 31) >> 3) * 16 + (pos & 15)) * 8 + (d & 7)] = f2b(lat[j]);
-      vp[vbase + ((size_t)(d >> 4) * (T32 >> 5) + (pos >> 5)) * 512
-         + (((pos & 31) >> 3) * 16 + (d & 15)) * 8 + (pos & 7)] = f2b(lat[j]);
+      kp[ktile + kfrag_off(d, pos)] = f2b(lat[j]);
+      vp[vhead + vfrag_off(d, pos, tiles32)] = f2b(lat[j]);
     }
   }
   if (lane < 32) {
     rrow[lane] = f2b(r1);
     rrow[lane + 32] = f2b(r2);
     if (kp) {
-      const int d1 = MLA_LAT + lane, d2 = MLA_LAT + lane + 32;
-      kp[kbase + (size_t)(d1 >> 5) * 512 + (((d1 & 31) >> 3) * 16 + (pos & 15)) * 8 + (d1 & 7)] = f2b(r1);
-      kp[kbase + (size_t)(d2 >> 5) * 512 + (((d2 & 31) >> 3) * 16 + (pos & 15)) * 8 + (d2 & 7)] = f2b(r2);
+      kp[ktile + kfrag_off(d1, pos)] = f2b(r1);
+      kp[ktile + kfrag_off(d2, pos)] = f2b(r2);
     }
   }
   if (kp8) {
@@ -1219,25 +1269,19 @@ __global__ __launch_bounds__(256) void mla_prep_append_kernel(
     float mx = fmaxf(fabsf(r1), fabsf(r2));
 #pragma unroll
     for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(lat[j]));
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
-    const float scl = fmaxf(mx, 1e-12f) / 448.f;
+    const float scl = e4m3_scale(wave_max(mx));
     const float qinv = 1.f / scl;
     if (lane == 0) ks[(size_t)b * T32 + pos] = scl;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int d = lane * 8 + j;
-      const unsigned short pk = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(lat[j] * qinv, 0.f, 0, false);
-      kp8[kbase + (size_t)(d >> 5) * 512 + (((d & 31) >> 3) * 16 + (pos & 15)) * 8 + (d & 7)] = (unsigned char)(pk & 0xff);
-      vp8[vbase + ((size_t)(d >> 4) * (T32 >> 5) + (pos >> 5)) * 512
-          + (((pos & 31) >> 3) * 16 + (d & 15)) * 8 + (pos & 7)] = (unsigned char)(pk & 0xff);
+      const unsigned char q8 = to_e4m3(lat[j] * qinv);
+      kp8[ktile + kfrag_off(d, pos)] = q8;
+      vp8[vhead + vfrag_off(d, pos, tiles32)] = q8;
     }
     if (lane < 32) {
-      const int d1 = MLA_LAT + lane, d2 = MLA_LAT + lane + 32;
-      const unsigned short p1 = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(r1 * qinv, 0.f, 0, false);
-      const unsigned short p2 = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(r2 * qinv, 0.f, 0, false);
-      kp8[kbase + (size_t)(d1 >> 5) * 512 + (((d1 & 31) >> 3) * 16 + (pos & 15)) * 8 + (d1 & 7)] = (unsigned char)(p1 & 0xff);
-      kp8[kbase + (size_t)(d2 >> 5) * 512 + (((d2 & 31) >> 3) * 16 + (pos & 15)) * 8 + (d2 & 7)] = (unsigned char)(p2 & 0xff);
+      kp8[ktile + kfrag_off(d1, pos)] = to_e4m3(r1 * qinv);
+      kp8[ktile + kfrag_off(d2, pos)] = to_e4m3(r2 * qinv);
     }
   }
 }
@@ -1262,19 +1306,9 @@ __global__ __launch_bounds__(256) void mla_q_prep_kernel(
 #pragma unroll
   for (int j = 0; j < 8; ++j) lv[j] = b2f(lsrc[lane * 8 + j]);
   float r1 = 0.f, r2 = 0.f;
-  if (lane < 32) {
-    const int pos = positions[(npos == B) ? b : 0];
-    const float c = cosb[(size_t)pos * 32 + lane];
-    const float sn = sinb[(size_t)pos * 32 + lane];
-    const unsigned short* qrot = q + (size_t)b * q_bstride + (size_t)h * (nope + MLA_ROPE) + nope;
-    int i1, i2;
-    if (interleave) { i1 = lane * 2; i2 = lane * 2 + 1; }
-    else            { i1 = lane;     i2 = lane + 32;    }
-    const float x1 = b2f(qrot[i1]);
-    const float x2 = b2f(qrot[i2]);
-    r1 = x1 * c - x2 * sn;
-    r2 = x2 * c + x1 * sn;
-  }
+  if (lane < 32)
+    mla_rope_pair(q + (size_t)b * q_bstride + (size_t)h * (nope + MLA_ROPE) + nope, cosb, sinb,
+                  row_position(positions, npos, B, 1, b), lane, interleave, r1, r2);
   if (q8 == nullptr) {
     unsigned short* dst = qfull + ((size_t)b * H + h) * MLA_DQK;
 #pragma unroll
@@ -1289,22 +1323,15 @@ __global__ __launch_bounds__(256) void mla_q_prep_kernel(
   float mx = fmaxf(fabsf(r1), fabsf(r2));
 #pragma unroll
   for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(lv[j]));
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
-  const float scl = fmaxf(mx, 1e-12f) / 448.f;
+  const float scl = e4m3_scale(wave_max(mx));
   const float inv = 1.f / scl;
   if (lane == 0) sq[(size_t)b * H + h] = scl;
   unsigned char* dst8 = q8 + ((size_t)b * H + h) * MLA_DQK;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const unsigned short pk = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(lv[j] * inv, 0.f, 0, false);
-    dst8[lane * 8 + j] = (unsigned char)(pk & 0xff);
-  }
+  for (int j = 0; j < 8; ++j) dst8[lane * 8 + j] = to_e4m3(lv[j] * inv);
   if (lane < 32) {
-    const unsigned short p1 = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(r1 * inv, 0.f, 0, false);
-    const unsigned short p2 = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(r2 * inv, 0.f, 0, false);
-    dst8[MLA_LAT + lane] = (unsigned char)(p1 & 0xff);
-    dst8[MLA_LAT + lane + 32] = (unsigned char)(p2 & 0xff);
+    dst8[MLA_LAT + lane] = to_e4m3(r1 * inv);
+    dst8[MLA_LAT + lane + 32] = to_e4m3(r2 * inv);
   }
 }
 
@@ -1316,24 +1343,18 @@ __global__ __launch_bounds__(256) void mla_append_kernel(
   const int wid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (wid >= B * S) return;
   const int lane = threadIdx.x & 63;
-  const int s = wid % S;
   const int b = wid / S;
-  const int pos = positions[(npos == B * S && npos != S) ? wid : s];
-  const unsigned short* lrow = lat + ((size_t)b * S + s) * MLA_LAT;
-  const unsigned short* rrow = rot + ((size_t)b * S + s) * MLA_ROPE;
-  const size_t kbase = (size_t)b * (T32 >> 4) * MLA_CHQK * 512 + (size_t)(pos >> 4) * MLA_CHQK * 512;
-  const size_t vbase = (size_t)b * MLA_GPV * (T32 >> 5) * 512;
+  const int pos = row_position(positions, npos, B, S, wid);
+  const unsigned short* lrow = lat + (size_t)wid * MLA_LAT;
+  const unsigned short* rrow = rot + (size_t)wid * MLA_ROPE;
+  const size_t ktile = ((size_t)b * (T32 >> 4) + (pos >> 4)) * MLA_KTILE;
+  const size_t vhead = (size_t)b * MLA_GPV * (T32 >> 5) * FRAG;
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
     const int d = lane * 9 + i;
     const unsigned short v = (d < MLA_LAT) ? lrow[d] : rrow[d - MLA_LAT];
-    // K-fragment image (16 pos x 32 dims per chunk)
-    kp[kbase + (size_t)(d >> 5) * 512 + (((d & 31) >> 3) * 16 + (pos & 15)) * 8 + (d & 7)] = v;
-    if (d < MLA_LAT) {
-      // V-fragment image (32 pos x 16 dims per group)
-      vp[vbase + ((size_t)(d >> 4) * (T32 >> 5) + (pos >> 5)) * 512
-         + (((pos & 31) >> 3) * 16 + (d & 15)) * 8 + (pos & 7)] = v;
-    }
+    kp[ktile + kfrag_off(d, pos)] = v;
+    if (d < MLA_LAT) vp[vhead + vfrag_off(d, pos, T32 >> 5)] = v;
   }
 }
 
@@ -1380,8 +1401,8 @@ __global__ __launch_bounds__(256) void attn_decode_mla_kernel(
 #pragma unroll
   for (int g = 0; g < MLA_GPV; ++g) acco[g] = (floatx4)(0.f);
 
-  const size_t kbase = (size_t)b * (T32 >> 4) * MLA_CHQK * 512;
-  const size_t vbase = (size_t)b * MLA_GPV * (T32 >> 5) * 512;
+  const size_t kbase = (size_t)b * (T32 >> 4) * MLA_KTILE;
+  const size_t vbase = (size_t)b * MLA_GPV * (T32 >> 5) * FRAG;
   const int col = lane & 15;
 
   for (int t = c0; t < c1; t += 32) {
@@ -1449,18 +1470,8 @@ __global__ __launch_bounds__(256) void attn_decode_mla_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) lsum[r] = lsum[r] * alpha[r] + rsum[r];
     float s_pv = 1.f, rfac = 1.f;
-    if (FP8) {
-      float mv = ks[(size_t)b * T32 + min(t + (lane & 31), T32 - 1)];
-#pragma unroll
-      for (int m_ = 32; m_ > 0; m_ >>= 1) mv = fmaxf(mv, __shfl_xor(mv, m_));
-      s_pv = fmaxf(mv, 1e-12f);
-      rfac = Rscale / s_pv;
-      Rscale = s_pv;
-    }
-#pragma unroll
-    for (int g = 0; g < MLA_GPV; ++g)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acco[g][r] *= alpha[r] * (FP8 ? rfac : 1.f);
+    if (FP8) s_pv = attn_fp8_pv_scale(ks + (size_t)b * T32, t, T32, lane, Rscale, rfac);
+    attn_rescale(acco, alpha, rfac);
     long pf8 = 0;
     bf16x8 pf;
     if (FP8) {
@@ -1511,27 +1522,6 @@ __global__ __launch_bounds__(256) void attn_decode_mla_kernel(
         ws_ml[pidx * 2 + 1] = lsum[r];
       }
     }
-  }
-}
-
-// wide merge for the MLA 512-dim latent output: 256 threads, 2 dims each
-__global__ __launch_bounds__(256) void attn_decode_merge512(
-    const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
-    unsigned short* __restrict__ out, int nsplit) {
-  const int bh = blockIdx.x;
-  float M = -INFINITY;
-  for (int i = 0; i < nsplit; ++i) M = fmaxf(M, ws_ml[((size_t)bh * nsplit + i) * 2 + 0]);
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int d = threadIdx.x + e * 256;
-    float L = 0.f, O = 0.f;
-    for (int i = 0; i < nsplit; ++i) {
-      const float lg = ws_ml[((size_t)bh * nsplit + i) * 2 + 1];
-      const float alpha = (lg > 0.f) ? __expf(ws_ml[((size_t)bh * nsplit + i) * 2 + 0] - M) : 0.f;
-      L += alpha * lg;
-      O += alpha * ws_o[((size_t)bh * nsplit + i) * MLA_LAT + d];
-    }
-    out[(size_t)bh * MLA_LAT + d] = f2b(L > 0.f ? O / L : 0.f);
   }
 }
 
@@ -2106,25 +2096,16 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(
 #pragma unroll
     for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(b2f(v[j])));
   }
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
+  mx = wave_max(mx);
   __shared__ float red[4];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
   __syncthreads();
+  // not e4m3_scale: an all-zero row keeps scale 1 / inv 0 here
   const float scale = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) / 448.f;
   const float inv = (scale > 0.f) ? 1.f / scale : 0.f;
   if (threadIdx.x == 0) sx[row] = (scale > 0.f) ? scale : 1.f;
   for (long long i = threadIdx.x * 8; i < K; i += 256 * 8) {
-    ushort8 v = *(const ushort8*)(xr + i);
-    unsigned char o[8];
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-      const float a = b2f(v[j]) * inv, b = b2f(v[j + 1]) * inv;
-      const unsigned short pk = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-      o[j] = (unsigned char)(pk & 0xff);
-      o[j + 1] = (unsigned char)(pk >> 8);
-    }
-    *(unsigned long long*)(qr + i) = *(unsigned long long*)o;
+    *(long*)(qr + i) = to_e4m3x8(*(const bf16x8*)(xr + i), inv);
   }
 }
 
@@ -2161,6 +2142,59 @@ __global__ __launch_bounds__(256) void skinny_combine_kernel(
 
 static inline hipStream_t cur_stream() {
   return (hipStream_t)c10::hip::getCurrentHIPStream().stream();
+}
+
+// runtime value -> compile-time tag handed to a generic lambda
+template <int V>
+using IntC = std::integral_constant<int, V>;
+
+// v in 1..8 -> f(IntC<v>)
+template <class F>
+static void dispatch_1to8(int v, const char* what, F&& f) {
+  switch (v) {
+    case 1: f(IntC<1>{}); break;
+    case 2: f(IntC<2>{}); break;
+    case 3: f(IntC<3>{}); break;
+    case 4: f(IntC<4>{}); break;
+    case 5: f(IntC<5>{}); break;
+    case 6: f(IntC<6>{}); break;
+    case 7: f(IntC<7>{}); break;
+    case 8: f(IntC<8>{}); break;
+    default: TORCH_CHECK(false, what, " out of range: ", v);
+  }
+}
+
+// v -> f(std::true_type / std::false_type)
+template <class F>
+static void dispatch_bool(bool v, F&& f) {
+  if (v) f(std::true_type{}); else f(std::false_type{});
+}
+
+// packed-cache arguments of the append kernels: bf16 copies, or e4m3 copies
+// (uint8 tensors), which come with fp32 scale tensors
+struct PackedCachePtrs {
+  unsigned short* kp = nullptr;
+  unsigned short* vp = nullptr;
+  unsigned char* kp8 = nullptr;
+  unsigned char* vp8 = nullptr;
+};
+
+static PackedCachePtrs packed_cache_ptrs(const torch::Tensor& kp, const torch::Tensor& vp) {
+  CHK(kp.is_contiguous() && vp.is_contiguous());
+  PackedCachePtrs p;
+  if (kp.dtype() == torch::kUInt8) {
+    p.kp8 = (unsigned char*)kp.data_ptr();
+    p.vp8 = (unsigned char*)vp.data_ptr();
+  } else {
+    p.kp = (unsigned short*)kp.data_ptr();
+    p.vp = (unsigned short*)vp.data_ptr();
+  }
+  return p;
+}
+
+static float* fp8_scale_ptr(const c10::optional<torch::Tensor>& s) {
+  CHK(s.has_value() && s->dtype() == torch::kFloat32 && s->is_contiguous());
+  return s->data_ptr<float>();
 }
 
 // split-K tile threshold for the skinny GEMMs: if the n-tile grid alone
@@ -2221,28 +2255,17 @@ void rope_qkv_append(torch::Tensor qkv, torch::Tensor cos, torch::Tensor sin,
   const int npos = (int)positions.numel();
   CHK(npos == S || npos == B * S);
   CHK(positions.is_contiguous());
-  unsigned short* kpc = nullptr;
-  unsigned short* vpc = nullptr;
-  unsigned char* kp8 = nullptr;
-  unsigned char* vp8 = nullptr;
+  PackedCachePtrs pc;
   float* skp = nullptr;
   float* svp = nullptr;
   int T32 = 0;
   if (kp.has_value() && vp.has_value()) {
-    CHK(hd == 128 && kp->is_contiguous() && vp->is_contiguous());
+    CHK(hd == 128);
     T32 = (int)kp->size(2) * 16;
-    if (kp->dtype() == torch::kUInt8) {
-      // fp8 packed mode: per-row e4m3 scales required
-      CHK(k_scale.has_value() && v_scale.has_value());
-      CHK(k_scale->dtype() == torch::kFloat32 && k_scale->is_contiguous());
-      CHK(v_scale->dtype() == torch::kFloat32 && v_scale->is_contiguous());
-      kp8 = (unsigned char*)kp->data_ptr();
-      vp8 = (unsigned char*)vp->data_ptr();
-      skp = k_scale->data_ptr<float>();
-      svp = v_scale->data_ptr<float>();
-    } else {
-      kpc = (unsigned short*)kp->data_ptr();
-      vpc = (unsigned short*)vp->data_ptr();
+    pc = packed_cache_ptrs(*kp, *vp);
+    if (pc.kp8) {
+      skp = fp8_scale_ptr(k_scale);
+      svp = fp8_scale_ptr(v_scale);
     }
   }
   const unsigned short* qnp = nullptr;
@@ -2260,27 +2283,40 @@ void rope_qkv_append(torch::Tensor qkv, torch::Tensor cos, torch::Tensor sin,
   hipLaunchKernelGGL(rope_qkv_append_kernel, dim3(blocks), dim3(256), 0, cur_stream(),
                      (unsigned short*)qkv.data_ptr(), cos.data_ptr<float>(), sin.data_ptr<float>(),
                      positions.data_ptr<int>(), (unsigned short*)kc.data_ptr(),
-                     (unsigned short*)vc.data_ptr(), B, S, H, KVH, hd, T, kpc, vpc, T32,
-                     qnp, knp, (float)norm_eps, npos, kp8, vp8, skp, svp);
+                     (unsigned short*)vc.data_ptr(), B, S, H, KVH, hd, T, pc.kp, pc.vp, T32,
+                     qnp, knp, (float)norm_eps, npos, pc.kp8, pc.vp8, skp, svp);
 }
 
-template <int HD>
-static void launch_attn_partial(int NQ, const unsigned short* q, const unsigned short* kc,
-                                const unsigned short* vc, const int* sl, float* ws_o, float* ws_ml,
-                                int B, int H, int KVH, int T, int nsplit, int qh0, float scale,
-                                long long q_stride, hipStream_t stream) {
-  const dim3 grid(B * KVH * nsplit), block(256);
-#define CASE(NQV) \
-  case NQV: \
-    hipLaunchKernelGGL((attn_decode_partial<NQV, HD>), grid, block, 0, stream, q, kc, vc, sl, \
-                       ws_o, ws_ml, B, H, KVH, T, nsplit, qh0, scale, q_stride); \
-    break;
-  switch (NQ) {
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-    default: TORCH_CHECK(false, "unsupported q-heads-per-kv-head slice: ", NQ);
+// Split-KV decode scaffolding shared by attn_decode, attn_decode_mfma and
+// attn_decode_mla: the fp32 partial workspace (o[hd] and (m, l) per
+// (b * H + head, split)), the bf16 output, and the merge launch.
+struct SplitKV {
+  torch::Tensor ws_o, ws_ml, out;
+  int BH, nsplit, hd;
+  SplitKV(const torch::Tensor& q, at::IntArrayRef out_shape, int BH, int nsplit, int hd)
+      : BH(BH), nsplit(nsplit), hd(hd) {
+    auto opts = torch::TensorOptions().dtype(torch::kFloat32).device(q.device());
+    ws_o = torch::empty({(long)BH * nsplit * hd}, opts);
+    ws_ml = torch::empty({(long)BH * nsplit * 2}, opts);
+    out = torch::empty(out_shape, torch::TensorOptions().dtype(torch::kBFloat16).device(q.device()));
   }
-#undef CASE
-}
+  float* o() const { return ws_o.data_ptr<float>(); }
+  float* ml() const { return ws_ml.data_ptr<float>(); }
+  torch::Tensor merge(hipStream_t stream) const {
+    auto launch = [&](auto hdc) {
+      constexpr int HD = decltype(hdc)::value;
+      hipLaunchKernelGGL((attn_decode_merge<HD>), dim3(BH), dim3(HD > 128 ? 256 : 128), 0, stream,
+                         o(), ml(), (unsigned short*)out.data_ptr(), nsplit);
+    };
+    switch (hd) {
+      case 64: launch(IntC<64>{}); break;
+      case 128: launch(IntC<128>{}); break;
+      case MLA_LAT: launch(IntC<MLA_LAT>{}); break;
+      default: TORCH_CHECK(false, "split-KV merge: unsupported head dim ", hd);
+    }
+    return out;
+  }
+};
 
 torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor seq_lens) {
   // q may be a strided view into the packed qkv tensor: [B, 1, H, hd] with an
@@ -2296,33 +2332,22 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, t
   // fill the 256 CUs: at least ~512 workgroups, chunks >= 128 positions
   int nsplit = std::max(1, 512 / std::max(1, B * KVH));
   nsplit = std::min<int>(nsplit, std::max(1, (T + 127) / 128));
-  auto opts = torch::TensorOptions().dtype(torch::kFloat32).device(q.device());
-  auto ws_o = torch::empty({(long)B * H * nsplit * hd}, opts);
-  auto ws_ml = torch::empty({(long)B * H * nsplit * 2}, opts);
-  auto out = torch::empty({q.size(0), q.size(1), q.size(2), q.size(3)},
-                          torch::TensorOptions().dtype(torch::kBFloat16).device(q.device()));
+  const SplitKV kv(q, q.sizes(), B * H, nsplit, hd);
   const float scale = 1.0f / sqrtf((float)hd);
   auto stream = cur_stream();
+  // up to 8 q heads of each kv head per partial launch
   for (int qh0 = 0; qh0 < rep; qh0 += 8) {
-    const int nq = std::min(8, rep - qh0);
-    if (hd == 128)
-      launch_attn_partial<128>(nq, (const unsigned short*)q.data_ptr(), (const unsigned short*)kc.data_ptr(),
-                               (const unsigned short*)vc.data_ptr(), seq_lens.data_ptr<int>(),
-                               ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(), B, H, KVH, T, nsplit, qh0,
-                               scale, q_stride, stream);
-    else
-      launch_attn_partial<64>(nq, (const unsigned short*)q.data_ptr(), (const unsigned short*)kc.data_ptr(),
-                              (const unsigned short*)vc.data_ptr(), seq_lens.data_ptr<int>(),
-                              ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(), B, H, KVH, T, nsplit, qh0,
-                              scale, q_stride, stream);
+    dispatch_1to8(std::min(8, rep - qh0), "attn_decode: q-heads-per-kv-head slice", [&](auto nq) {
+      dispatch_bool(hd == 128, [&](auto wide) {
+        constexpr int NQ = decltype(nq)::value, HD = decltype(wide)::value ? 128 : 64;
+        hipLaunchKernelGGL((attn_decode_partial<NQ, HD>), dim3(B * KVH * nsplit), dim3(256), 0, stream,
+                           (const unsigned short*)q.data_ptr(), (const unsigned short*)kc.data_ptr(),
+                           (const unsigned short*)vc.data_ptr(), seq_lens.data_ptr<int>(),
+                           kv.o(), kv.ml(), B, H, KVH, T, nsplit, qh0, scale, q_stride);
+      });
+    });
   }
-  if (hd == 128)
-    hipLaunchKernelGGL((attn_decode_merge<128>), dim3(B * H), dim3(128), 0, stream,
-                       ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(), (unsigned short*)out.data_ptr(), nsplit);
-  else
-    hipLaunchKernelGGL((attn_decode_merge<64>), dim3(B * H), dim3(128), 0, stream,
-                       ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(), (unsigned short*)out.data_ptr(), nsplit);
-  return out;
+  return kv.merge(stream);
 }
 
 // q: [B, 1, H, 128] (strided batch OK); kp/vp: the packed cache copies.
@@ -2352,27 +2377,24 @@ torch::Tensor attn_decode_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor 
   // the packed-cache stream deep while chunks stay >= 32 positions
   int nsplit = 1;
   while (B * KVH * nsplit * 2 < 4096 && (T32 / (nsplit * 2)) >= 32 && nsplit < 32) nsplit *= 2;
-  auto opts = torch::TensorOptions().dtype(torch::kFloat32).device(q.device());
-  auto ws_o = torch::empty({(long)B * H * nsplit * hd}, opts);
-  auto ws_ml = torch::empty({(long)B * H * nsplit * 2}, opts);
-  auto out = torch::empty({q.size(0), q.size(1), q.size(2), q.size(3)},
-                          torch::TensorOptions().dtype(torch::kBFloat16).device(q.device()));
+  const SplitKV kv(q, q.sizes(), B * H, nsplit, hd);
   const float scale = (scale_in > 0.0) ? (float)scale_in : 1.0f / sqrtf((float)hd);
   auto stream = cur_stream();
   const int waves = B * KVH * nsplit;
   // default ON: measured -1.1 ms/step on 70B B=128 and -0.8 on 8B B=256
   const char* pf_env = getenv("XOT_ATTN_PREFETCH");
   const bool prefetch = (pf_env == nullptr) || (pf_env[0] != '0');
-#define ADM_LAUNCH(PF, F8)   hipLaunchKernelGGL((attn_decode_mfma_kernel<PF, F8>), dim3((waves + 3) / 4), dim3(256), 0, stream,                      (const unsigned short*)q.data_ptr(), (const unsigned short*)kp.data_ptr(),                      (const unsigned short*)vp.data_ptr(), seq_lens.data_ptr<int>(),                      ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(), B, H, KVH, T32, nsplit,                      scale, q_stride, (float)softcap, (int)window, skp, svp)
-  if (prefetch && fp8) ADM_LAUNCH(true, true);
-  else if (prefetch) ADM_LAUNCH(true, false);
-  else if (fp8) ADM_LAUNCH(false, true);
-  else ADM_LAUNCH(false, false);
-#undef ADM_LAUNCH
-  hipLaunchKernelGGL((attn_decode_merge<128>), dim3(B * H), dim3(128), 0, stream,
-                     ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(),
-                     (unsigned short*)out.data_ptr(), nsplit);
-  return out;
+  dispatch_bool(prefetch, [&](auto pf) {
+    dispatch_bool(fp8, [&](auto f8) {
+      hipLaunchKernelGGL((attn_decode_mfma_kernel<decltype(pf)::value, decltype(f8)::value>),
+                         dim3((waves + 3) / 4), dim3(256), 0, stream,
+                         (const unsigned short*)q.data_ptr(), (const unsigned short*)kp.data_ptr(),
+                         (const unsigned short*)vp.data_ptr(), seq_lens.data_ptr<int>(),
+                         kv.o(), kv.ml(), B, H, KVH, T32, nsplit, scale, q_stride,
+                         (float)softcap, (int)window, skp, svp);
+    });
+  });
+  return kv.merge(stream);
 }
 
 // q: [B, S, H, 128] (strided over b/s OK, head rows contiguous); kp/vp: the
@@ -2472,27 +2494,20 @@ std::vector<torch::Tensor> mla_q_prep(torch::Tensor q, torch::Tensor q_lat, torc
   const int npos = (int)positions.numel();
   CHK(npos == 1 || npos == B);
   const int waves = B * H;
-  if (fp8) {
-    auto q8 = torch::empty({(long)B, (long)H, (long)MLA_DQK},
-                           torch::TensorOptions().dtype(torch::kUInt8).device(q.device()));
-    auto sq = torch::empty({(long)B, (long)H},
-                           torch::TensorOptions().dtype(torch::kFloat32).device(q.device()));
-    hipLaunchKernelGGL(mla_q_prep_kernel, dim3((waves + 3) / 4), dim3(256), 0, cur_stream(),
-                       (const unsigned short*)q.data_ptr(), (const unsigned short*)q_lat.data_ptr(),
-                       cos.data_ptr<float>(), sin.data_ptr<float>(), positions.data_ptr<int>(),
-                       nullptr, B, H, (long long)H * (nope + MLA_ROPE),
-                       (int)nope, interleave ? 1 : 0, npos,
-                       (unsigned char*)q8.data_ptr(), sq.data_ptr<float>());
-    return {q8, sq};
-  }
-  auto qfull = torch::empty({(long)B, (long)H, (long)MLA_DQK},
-                            torch::TensorOptions().dtype(torch::kBFloat16).device(q.device()));
+  // bf16: {qfull}; fp8: {q8, one scale per (b, h)}
+  auto qout = torch::empty({(long)B, (long)H, (long)MLA_DQK},
+                           q.options().dtype(fp8 ? torch::kUInt8 : torch::kBFloat16));
+  torch::Tensor sq;
+  if (fp8) sq = torch::empty({(long)B, (long)H}, q.options().dtype(torch::kFloat32));
   hipLaunchKernelGGL(mla_q_prep_kernel, dim3((waves + 3) / 4), dim3(256), 0, cur_stream(),
                      (const unsigned short*)q.data_ptr(), (const unsigned short*)q_lat.data_ptr(),
                      cos.data_ptr<float>(), sin.data_ptr<float>(), positions.data_ptr<int>(),
-                     (unsigned short*)qfull.data_ptr(), B, H, (long long)H * (nope + MLA_ROPE),
-                     (int)nope, interleave ? 1 : 0, npos, nullptr, nullptr);
-  return {qfull};
+                     fp8 ? nullptr : (unsigned short*)qout.data_ptr(), B, H,
+                     (long long)H * (nope + MLA_ROPE), (int)nope, interleave ? 1 : 0, npos,
+                     fp8 ? (unsigned char*)qout.data_ptr() : nullptr,
+                     fp8 ? sq.data_ptr<float>() : nullptr);
+  if (fp8) return {qout, sq};
+  return {qout};
 }
 
 // ckv: [B, S, 576] raw kv_a output; w: [512] bf16 norm weight; cos/sin
@@ -2513,26 +2528,14 @@ void mla_prep_append(torch::Tensor ckv, torch::Tensor w, torch::Tensor cos,
   const int npos = (int)positions.numel();
   CHK(npos == S || npos == B * S);
   const int waves = B * S;
-  unsigned short* kpc = nullptr;
-  unsigned short* vpc = nullptr;
-  unsigned char* kp8 = nullptr;
-  unsigned char* vp8 = nullptr;
-  float* ksp = nullptr;
-  if (kp.dtype() == torch::kUInt8) {
-    CHK(k_scale.has_value() && k_scale->dtype() == torch::kFloat32 && k_scale->is_contiguous());
-    kp8 = (unsigned char*)kp.data_ptr();
-    vp8 = (unsigned char*)vp.data_ptr();
-    ksp = k_scale->data_ptr<float>();
-  } else {
-    kpc = (unsigned short*)kp.data_ptr();
-    vpc = (unsigned short*)vp.data_ptr();
-  }
+  const PackedCachePtrs pc = packed_cache_ptrs(kp, vp);
+  float* ksp = pc.kp8 ? fp8_scale_ptr(k_scale) : nullptr;
   hipLaunchKernelGGL(mla_prep_append_kernel, dim3((waves + 3) / 4), dim3(256), 0, cur_stream(),
                      (const unsigned short*)ckv.data_ptr(), (const unsigned short*)w.data_ptr(),
                      cos.data_ptr<float>(), sin.data_ptr<float>(), positions.data_ptr<int>(),
                      (unsigned short*)lat_c.data_ptr(), (unsigned short*)rot_c.data_ptr(),
-                     kpc, vpc, B, S, T, T32, (float)eps, interleave ? 1 : 0, npos,
-                     kp8, vp8, ksp);
+                     pc.kp, pc.vp, B, S, T, T32, (float)eps, interleave ? 1 : 0, npos,
+                     pc.kp8, pc.vp8, ksp);
 }
 
 // lat: [B, S, 512] bf16 (post-RMSNorm latent), rot: [B, S, 64] bf16 (roped
@@ -2576,11 +2579,7 @@ torch::Tensor attn_decode_mla(torch::Tensor q, torch::Tensor kp, torch::Tensor v
   // 1.1 TB/s; 256+ WGs is the floor for the packed stream.
   int nsplit = 1;
   while (B * hgroups * nsplit * 2 < 4096 && (T32 / (nsplit * 2)) >= 16 && nsplit < 64) nsplit *= 2;
-  auto opts = torch::TensorOptions().dtype(torch::kFloat32).device(q.device());
-  auto ws_o = torch::empty({(long)B * H * nsplit * MLA_LAT}, opts);
-  auto ws_ml = torch::empty({(long)B * H * nsplit * 2}, opts);
-  auto out = torch::empty({(long)B, (long)H, (long)MLA_LAT},
-                          torch::TensorOptions().dtype(torch::kBFloat16).device(q.device()));
+  const SplitKV kv(q, {(long)B, (long)H, (long)MLA_LAT}, B * H, nsplit, MLA_LAT);
   const float scale = (scale_in > 0.0) ? (float)scale_in : 1.0f / sqrtf((float)MLA_DQK);
   auto stream = cur_stream();
   const int waves = B * hgroups * nsplit;
@@ -2591,21 +2590,13 @@ torch::Tensor attn_decode_mla(torch::Tensor q, torch::Tensor kp, torch::Tensor v
     sqp = q_scale->data_ptr<float>();
     ksp = k_scale->data_ptr<float>();
   }
-  if (fp8)
-    hipLaunchKernelGGL((attn_decode_mla_kernel<true>), dim3((waves + 3) / 4), dim3(256), 0, stream,
-                       (const unsigned short*)q.data_ptr(), (const unsigned short*)kp.data_ptr(),
-                       (const unsigned short*)vp.data_ptr(), seq_lens.data_ptr<int>(),
-                       ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(), B, H, T32, nsplit, scale,
-                       sqp, ksp);
-  else
-    hipLaunchKernelGGL((attn_decode_mla_kernel<false>), dim3((waves + 3) / 4), dim3(256), 0, stream,
-                       (const unsigned short*)q.data_ptr(), (const unsigned short*)kp.data_ptr(),
-                       (const unsigned short*)vp.data_ptr(), seq_lens.data_ptr<int>(),
-                       ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(), B, H, T32, nsplit, scale);
-  hipLaunchKernelGGL(attn_decode_merge512, dim3(B * H), dim3(256), 0, stream,
-                     ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(),
-                     (unsigned short*)out.data_ptr(), nsplit);
-  return out;
+  dispatch_bool(fp8, [&](auto f8) {
+    hipLaunchKernelGGL((attn_decode_mla_kernel<decltype(f8)::value>), dim3((waves + 3) / 4), dim3(256),
+                       0, stream, (const unsigned short*)q.data_ptr(),
+                       (const unsigned short*)kp.data_ptr(), (const unsigned short*)vp.data_ptr(),
+                       seq_lens.data_ptr<int>(), kv.o(), kv.ml(), B, H, T32, nsplit, scale, sqp, ksp);
+  });
+  return kv.merge(stream);
 }
 
 torch::Tensor mfma16_probe(torch::Tensor a, torch::Tensor b) {
@@ -2691,25 +2682,6 @@ static SkinnyPlan skinny_plan(long long N, long long K, long long E, int k_align
   return {ntiles, nsplit, kc, bk128};
 }
 
-template <int V>
-using IntC = std::integral_constant<int, V>;
-
-// runtime MT (1..8) -> f(IntC<MT>)
-template <class F>
-static void skinny_dispatch_mt(int MT, F&& f) {
-  switch (MT) {
-    case 1: f(IntC<1>{}); break;
-    case 2: f(IntC<2>{}); break;
-    case 3: f(IntC<3>{}); break;
-    case 4: f(IntC<4>{}); break;
-    case 5: f(IntC<5>{}); break;
-    case 6: f(IntC<6>{}); break;
-    case 7: f(IntC<7>{}); break;
-    case 8: f(IntC<8>{}); break;
-    default: TORCH_CHECK(false, "skinny GEMM: MT out of range");
-  }
-}
-
 // what a launcher's kernel call needs besides its own operands
 struct SkinnyLaunch {
   dim3 grid;
@@ -2743,7 +2715,7 @@ static torch::Tensor skinny_run(const torch::Tensor& x, at::IntArrayRef ysizes, 
                        is_split ? nullptr : (unsigned short*)y.data_ptr(),
                        is_split ? P.data_ptr<float>() : nullptr,
                        is_split ? nullptr : bptr, p.kc, p.nsplit};
-  skinny_dispatch_mt((int)(rows / 32), [&](auto mt) {
+  dispatch_1to8((int)(rows / 32), "skinny GEMM: MT", [&](auto mt) {
     auto with_split = [&](auto split) {
       if constexpr (HAS_BK128) {
         if (p.bk128) return launch(mt, split, IntC<128>{}, L);
