@@ -50,6 +50,13 @@ def _time_us(fn, reps=4, rounds=3) -> float:
   return best
 
 
+def _packed_epilogue(fn, x, wp, N, bias, epilogue):
+  """Packed decode GEMM `fn` with its row epilogue -> (h', normed | None)."""
+  res, w, eps = epilogue
+  out = fn(x, wp, N, bias, res.contiguous(), w, eps, 0.0)
+  return out[0], (out[1] if w is not None else None)
+
+
 class XotLinear(nn.Linear):
   """nn.Linear with an optional decode-path prepack: `pack_decode()` stores a
   second copy of the weight in MFMA A-fragment order ([N/32,K/16,64,8], see
@@ -113,7 +120,17 @@ class XotLinear(nn.Linear):
       y = y + self.bias
     return y.view(list(x.shape[:-1]) + [N])
 
-  def forward(self, x):
+  def forward(self, x, epilogue=None):
+    """epilogue = (residual, norm_weight | None, eps) turns the result into
+    (h' = y + residual, rmsnorm(h') | None): inside the packed kernel's
+    split-K combine where that path is picked, else one add_rmsnorm launch."""
+    y = self._gemm(x, epilogue)
+    if epilogue is None or isinstance(y, tuple):
+      return y
+    res, w, eps = epilogue
+    return ops.add_rmsnorm(y, res.view(y.shape), w, eps)
+
+  def _gemm(self, x, epilogue=None):
     if (x.is_cuda and x.dtype == torch.bfloat16 and not torch.is_grad_enabled()
         and os.getenv("XOT_FP8_PREFILL", "0") == "1"):
       N, K = self.weight.shape
@@ -167,6 +184,9 @@ class XotLinear(nn.Linear):
           if use == "xreg":
             return hip.skinny_gemm_packed_xreg(x, self.weight_packed, N, self.bias)
           if use == "packed":
+            if epilogue is not None:
+              return _packed_epilogue(hip.skinny_gemm_packed_epilogue, x, self.weight_packed, N,
+                                      self.bias, epilogue)
             return hip.skinny_gemm_packed(x, self.weight_packed, N, self.bias)
     return ops.linear(x, self.weight, self.bias)
 
@@ -260,7 +280,8 @@ class MLP(nn.Module):
     self.gate_up_proj = XotLinear(cfg.dim, 2 * I, bias=False)
     self.down_proj = XotLinear(I, cfg.dim, bias=False)
 
-  def forward(self, x):
+  def forward(self, x, epilogue=None):
+    """epilogue: see XotLinear.forward — the down projection carries it."""
     gu = self.gate_up_proj(x)
     dp = self.down_proj
     if (getattr(dp, "weight_packed", None) is not None and gu.is_cuda and gu.dtype == torch.bfloat16
@@ -288,8 +309,13 @@ class MLP(nn.Module):
                 print(f"[xot] swiglu-fuse auto-pick N={N} I={I} M={M}: fused {t_fused:.1f} us "
                       f"vs split {t_split:.1f} us -> {use}", flush=True)
           if use == "fused":
+            if epilogue is not None:
+              return _packed_epilogue(hip.skinny_gemm_packed_swiglu_epilogue, gu, dp.weight_packed,
+                                      N, dp.bias, epilogue)
             y = hip.skinny_gemm_packed_swiglu(gu, dp.weight_packed, N, dp.bias)
             return y.view(list(x.shape[:-1]) + [N])
+    if epilogue is not None:
+      return self.down_proj(ops.swiglu_packed(gu), epilogue)
     return self.down_proj(ops.swiglu_packed(gu))
 
 
@@ -481,6 +507,22 @@ class DecoderLayer(nn.Module):
     normed, h = ops.rmsnorm_residual(attn_out, x, self.post_attention_layernorm.weight, self.eps)
     return h + self.mlp(normed)
 
+  def forward_carry(self, x, normed_in, next_norm_w, cos, sin, positions, kv, start_pos, is_decode,
+                    seq_lens=None):
+    """Inference forward that carries the following norm: returns
+    (h', rmsnorm(h') by next_norm_w | None). normed_in is this layer's input
+    norm as the previous layer's epilogue produced it (None: computed here).
+    The closing residual add and that norm run in the down projection's row
+    epilogue instead of a combine, a torch add and a norm launch."""
+    if normed_in is None:
+      normed_in = self.input_layernorm(x)
+    attn_out = self.self_attn(normed_in, cos, sin, positions, kv, start_pos, is_decode, seq_lens)
+    normed, h = ops.rmsnorm_residual(attn_out, x, self.post_attention_layernorm.weight, self.eps)
+    epilogue = (h, next_norm_w, self.eps)
+    if isinstance(self.mlp, MLP):
+      return self.mlp(normed, epilogue)
+    return ops.add_rmsnorm(self.mlp(normed), h, next_norm_w, self.eps)
+
 
 class ShardedModel(nn.Module):
   """The layer range [shard.start_layer .. shard.end_layer] of one model."""
@@ -594,12 +636,17 @@ class ShardedModel(nn.Module):
     is_decode: bool = False,
     seq_lens: Optional[torch.Tensor] = None,
     last_only: bool = True,
+    carry_norm: Optional[bool] = None,
   ) -> torch.Tensor:
     """Run this shard.
 
     x: [B,S] int tokens (first shard) or [B,S,D] hidden states.
     caches: one (k_cache, v_cache) pair per LOCAL layer.
     positions: absolute position ids [S] or [B,S] (device tensor).
+    carry_norm: every layer computes the norm that follows it in its down
+    projection's epilogue (DecoderLayer.forward_carry). None = on for GPU
+    bf16 inference with XOT_FUSE_EPILOGUE unset or 1; training, the
+    cache-free forward and the CPU path keep the per-layer norms.
     Returns hidden [B,S,D] for non-last shards; logits for the last
     ([B,V] when is_decode/last_only, else [B,S,V]).
     """
@@ -614,10 +661,27 @@ class ShardedModel(nn.Module):
     # per-layer activation residency for a recompute in backward
     use_ckpt = (caches is None and self.training and torch.is_grad_enabled()
                 and os.getenv("XOT_ACT_CKPT", "0") == "1")
-    for idx, lid in enumerate(self.local_layer_ids):
+    if carry_norm is None:
+      carry_norm = (h.is_cuda and h.dtype == torch.bfloat16 and not torch.is_grad_enabled()
+                    and ops.fuse_epilogue_enabled())
+    carry_norm = bool(carry_norm) and caches is not None and not torch.is_grad_enabled()
+    normed = None  # the next norm of h, when the layer before has produced it
+    lids = self.local_layer_ids
+    for idx, lid in enumerate(lids):
       layer = self.layers[str(lid)]
       kv = caches[idx] if caches is not None else None
-      if use_ckpt:
+      if carry_norm:
+        # the norm that follows this layer: the next local layer's input norm,
+        # or the final norm where it will see this h unsliced
+        if idx + 1 < len(lids):
+          next_w = self.layers[str(lids[idx + 1])].input_layernorm.weight
+        elif self.shard.is_last_layer and not (last_only and h.shape[1] > 1):
+          next_w = self.norm.weight
+        else:
+          next_w = None
+        h, normed = layer.forward_carry(h, normed, next_w, cos, sin, positions, kv, start_pos,
+                                        is_decode, seq_lens)
+      elif use_ckpt:
         h = torch.utils.checkpoint.checkpoint(
           layer, h, cos, sin, positions, kv, start_pos, is_decode, seq_lens,
           use_reentrant=False)
@@ -627,7 +691,8 @@ class ShardedModel(nn.Module):
       return h
     if last_only and h.shape[1] > 1:
       h = h[:, -1:, :].contiguous()  # kernels require contiguous rows
-    h = self.norm(h)
+      normed = None
+    h = normed if normed is not None else self.norm(h)
     if hasattr(self, "lm_head"):
       logits = self.lm_head(h)  # XotLinear: packed decode kernel when prepacked
     else:

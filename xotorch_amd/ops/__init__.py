@@ -73,6 +73,27 @@ def rmsnorm_residual(
   return torch_ref.rmsnorm_residual(x, residual, weight, eps, w_bias)
 
 
+def add_rmsnorm(
+  y: torch.Tensor, residual: torch.Tensor, weight: Optional[torch.Tensor], eps: float,
+  w_bias: float = 0.0
+) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+  """(h' = y + residual, rmsnorm(h')) in one launch — the layer's closing
+  residual add fused with the norm that follows it; the norm reads the
+  rounded h'. weight=None gives (h', None)."""
+  tensors = (y, residual) if weight is None else (y, residual, weight)
+  if _use_hip(*tensors) and y.dtype == torch.bfloat16:
+    out = _hip.add_rmsnorm(y.contiguous(), residual.contiguous(), weight, eps, w_bias)
+    return out[0], (out[1] if weight is not None else None)
+  return torch_ref.add_rmsnorm(y, residual, weight, eps, w_bias)
+
+
+def fuse_epilogue_enabled() -> bool:
+  """XOT_FUSE_EPILOGUE (default 1, read per call): carry the next layer's
+  input norm in the down-projection's row epilogue; 0 keeps the separate
+  combine, add and norm launches."""
+  return os.getenv("XOT_FUSE_EPILOGUE", "1") != "0"
+
+
 def rope_apply(q, k, cos, sin, positions):
   """Standalone RoPE (training / oracle paths). On the GPU inference hot
   path RoPE is fused into rope_qkv_append — there is deliberately no

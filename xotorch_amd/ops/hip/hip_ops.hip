@@ -479,9 +479,11 @@ __global__ __launch_bounds__(256) void attn_decode_partial(
 //   online softmax row stats via 4 shfl_xor over the 16-lane column groups
 //   P -> bf16 A-fragments through a 96 B-stride LDS image (conflict-free)
 //   out[16q][128] += 8 x v_mfma_f32_16x16x32_bf16 (V streamed packed)
-// No cross-wave barriers (per-wave LDS slice), so ragged per-batch lengths
-// cannot deadlock. Partials go to the same (m, l, o) workspace as the VALU
-// kernel and are merged by attn_decode_merge<128>.
+// No cross-wave barriers in the position loop (per-wave LDS slice), so ragged
+// per-batch lengths cannot deadlock. With nsplit <= 4 the workgroup merges its
+// own splits after one barrier that every wave reaches (attn_merge_in_workgroup);
+// otherwise partials go to the same (m, l, o) workspace as the VALU kernel and
+// are merged by attn_decode_merge<128>.
 // Replaces the torchtune cached-decode step (reference general_mha.py:211-215);
 // the VALU split-KV kernel above stays as the hd=64 / unpacked-cache path.
 // ---------------------------------------------------------------------------
@@ -621,6 +623,60 @@ DEVINL void attn_store_partial(float* __restrict__ ws_o, float* __restrict__ ws_
   }
 }
 
+// In-workgroup split-KV merge (nsplit in {1, 2, 4}): the 4 / nsplit
+// (b, kv-head) groups of a workgroup hold every split of their rows, so the
+// waves exchange their partials through LDS and write final bf16 rows — no
+// workspace round trip, no merge launch. A wave's slab is 16 query rows of
+// ATTN_MROW floats: o[128], then m and l in the pad; 4 * 132 = 16 (mod 32)
+// keeps the four row groups of a store on distinct banks. The slab starts at
+// the wave's own P image, which is dead once its position loop has ended, so
+// the one barrier below is the only synchronisation needed.
+// The arithmetic and the split order are attn_decode_merge's, term for term:
+// the result is bit-identical to the workspace path.
+constexpr int ATTN_MROW = 132;
+constexpr int ATTN_MSLAB = 16 * ATTN_MROW;
+
+template <int NG>
+DEVINL void attn_merge_in_workgroup(float* __restrict__ lds, unsigned short* __restrict__ out,
+                                    const floatx4 (&acco)[NG], const float (&m)[4], const float (&lsum)[4],
+                                    int wv, int lane, int nq, int bh0, int nsplit, float oscale, bool live) {
+  static_assert(NG * 16 == 128, "merge slab rows hold 128 dims");
+  const int col = lane & 15;
+  float* mine = lds + wv * ATTN_MSLAB;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int qrow = (lane >> 4) * 4 + r;
+    if (live && qrow < nq) {
+#pragma unroll
+      for (int g = 0; g < NG; ++g) mine[qrow * ATTN_MROW + g * 16 + col] = acco[g][r] * oscale;
+      if (col == 0) {
+        mine[qrow * ATTN_MROW + 128] = m[r];
+        mine[qrow * ATTN_MROW + 129] = lsum[r];
+      }
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  // the group's nsplit waves share its nq rows; a lane owns dims 2*lane, 2*lane+1
+  const int split = wv % nsplit;
+  const float* grp = lds + (wv - split) * ATTN_MSLAB;
+  for (int row = split; row < nq; row += nsplit) {
+    const float* rp = grp + row * ATTN_MROW;
+    float M = -INFINITY;
+    for (int i = 0; i < nsplit; ++i) M = fmaxf(M, rp[i * ATTN_MSLAB + 128]);
+    float L = 0.f, O0 = 0.f, O1 = 0.f;
+    for (int i = 0; i < nsplit; ++i) {
+      const float lg = rp[i * ATTN_MSLAB + 129];
+      const float alpha = (lg > 0.f) ? __expf(rp[i * ATTN_MSLAB + 128] - M) : 0.f;
+      L += alpha * lg;
+      O0 += alpha * rp[i * ATTN_MSLAB + lane * 2];
+      O1 += alpha * rp[i * ATTN_MSLAB + lane * 2 + 1];
+    }
+    const unsigned int lo = f2b(L > 0.f ? O0 / L : 0.f), hi = f2b(L > 0.f ? O1 / L : 0.f);
+    *reinterpret_cast<unsigned int*>(out + (size_t)(bh0 + row) * 128 + lane * 2) = lo | (hi << 16);
+  }
+}
+
 // softcap > 0 applies gemma2's attention-logit soft-capping
 // (s = cap * tanh(s / cap), after scale, before masking); window > 0 is the
 // sliding-window mask (query at sl-1 sees positions [sl - window, sl)).
@@ -629,24 +685,37 @@ DEVINL void attn_store_partial(float* __restrict__ ws_o, float* __restrict__ ws_
 // sk/sv (appended by rope_qkv_append's fp8 mode) — half the stream bytes.
 // q is quantized per head in-kernel; scores rescale by s_q[row]*s_k[col];
 // PV keeps a per-tile running scale R (s_v folded into the quantized P).
+// 3 waves/SIMD is what the position loop reaches on its own (136 VGPR + 32
+// AGPR with PREFETCH); stated, because with the merge slabs in LDS the
+// register allocator otherwise spends a wave of occupancy (168 + 32).
 template <bool PREFETCH = false, bool FP8 = false>
-__global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
+__global__ __launch_bounds__(256, 3) void attn_decode_mfma_kernel(
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ kp,
     const unsigned short* __restrict__ vp, const int* __restrict__ seq_lens,
     float* __restrict__ ws_o, float* __restrict__ ws_ml,
     int B, int H, int KVH, int T32, int nsplit, float scale, long long q_stride,
     float softcap, int window,
-    const float* __restrict__ sk = nullptr, const float* __restrict__ sv = nullptr) {
+    const float* __restrict__ sk = nullptr, const float* __restrict__ sv = nullptr,
+    unsigned short* __restrict__ out = nullptr) {
   const int wv = threadIdx.x >> 6;
   const int wid = blockIdx.x * 4 + wv;
-  __shared__ unsigned short plds_all[4][16 * 48];  // 96 B row stride: bank-conflict-free b128 reads
-  if (wid >= B * KVH * nsplit) return;
-  const int split = wid % nsplit;
-  const int kvh = (wid / nsplit) % KVH;
-  const int b = wid / (nsplit * KVH);
+  // The kernel's one LDS object: each wave's merge slab, whose head doubles as
+  // its P image (16 rows, 96 B row stride: bank-conflict-free b128 reads).
+  // Declared in the P image's element type: declared as float and cast for
+  // the loop, the same kernel measured 60 us instead of 48 at B=128, sl=540.
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][ATTN_MSLAB * 2];
+  // out != null selects the in-workgroup merge: waves past the end (whole
+  // groups, as nsplit divides 4) then stay for its barrier with an empty
+  // position range and touch no global memory.
+  const bool live = wid < B * KVH * nsplit;
+  if (!live && out == nullptr) return;
+  const int widc = live ? wid : 0;
+  const int split = widc % nsplit;
+  const int kvh = (widc / nsplit) % KVH;
+  const int b = widc / (nsplit * KVH);
   const int lane = threadIdx.x & 63;
   const int NQ = H / KVH;
-  const int sl = seq_lens[b];
+  const int sl = live ? seq_lens[b] : 0;
   const int chunk = ((T32 / nsplit + 31) >> 5) << 5;
   const int win_lo = (window > 0) ? max(0, sl - window) : 0;  // first visible pos
   const int c0 = max(split * chunk, (win_lo >> 5) << 5);
@@ -664,9 +733,11 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
   float srow[4];
   {
     const unsigned short* qrow = q + (size_t)b * q_stride + (size_t)(qh_base + qi) * 128 + (lane >> 4) * 8;
-    bf16x8 qb[4];
+    bf16x8 qb[4] = {};
+    if (live) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) qb[c] = frag_load<false>(qrow + c * 32);
+      for (int c = 0; c < 4; ++c) qb[c] = frag_load<false>(qrow + c * 32);
+    }
     if constexpr (FP8) {
       // quantize per head: amax over the 4 lanes x 32 elements of the row
       float mx = 0.f;
@@ -756,9 +827,14 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
       acco[g] = F::mfma(pf, frag_load_nt<FP8>(vt + (size_t)g * (T32 >> 5) * FRAG), acco[g]);
   }
 
-  // ---- epilogue: one (m, l, o[128]) partial per (b, qh, split) ----
-  attn_store_partial(ws_o, ws_ml, acco, m, lsum, lane, NQ, b * H + qh_base, nsplit, split,
-                     FP8 ? Rscale : 1.f);
+  // ---- epilogue: final rows merged in the workgroup, or one (m, l, o[128])
+  // partial per (b, qh, split) for attn_decode_merge ----
+  if (out != nullptr)
+    attn_merge_in_workgroup(reinterpret_cast<float*>(&plds_all[0][0]), out, acco, m, lsum, wv, lane, NQ, b * H + qh_base, nsplit,
+                            FP8 ? Rscale : 1.f, live);
+  else
+    attn_store_partial(ws_o, ws_ml, acco, m, lsum, lane, NQ, b * H + qh_base, nsplit, split,
+                       FP8 ? Rscale : 1.f);
 }
 
 // ---------------------------------------------------------------------------
@@ -2134,6 +2210,114 @@ __global__ __launch_bounds__(256) void skinny_combine_kernel(
   }
 }
 
+// Row epilogue of the layer's last projection: combine + residual add + the
+// NEXT norm in one pass over the row, one workgroup per row.
+//   y  = bf16(sum of the fp32 split-K partials in split order + bias)
+//        (PARTIALS; what skinny_combine_kernel writes), or a finished bf16 y
+//   h' = bf16(y + res)                      (what the bf16 torch add writes)
+//   normed = rmsnorm(h') from the ROUNDED h', as rmsnorm_kernel<false> reads
+//            it back (w == null: h' only)
+// Every rounding point of the three-launch chain is kept, and the sum of
+// squares is rmsnorm_kernel's own: thread t of 256 owns elements
+// t*8 + c*2048 (c = 0..7), accumulates them in (c, j) order, then wave_sum and
+// the 4 wave partials. So h' and normed are bit-identical to the chain.
+// The workgroup is 1024 threads all the same: thread (q, t) = (tid >> 8,
+// tid & 255) streams chunks q and q + 4 of thread t's elements (a 128-row
+// decode batch is only 128 workgroups; 4 waves each leave the partials'
+// stream latency-bound at under half the combine's rate), parks the rounded
+// h' in LDS, and the first 256 threads replay rmsnorm_kernel's accumulation
+// from there.
+constexpr int EPI_Q = 4;  // 256-thread groups per workgroup
+
+template <bool PARTIALS>
+__global__ __launch_bounds__(EPI_Q * 256) void skinny_epilogue_kernel(
+    const float* __restrict__ P, const unsigned short* __restrict__ y,
+    const unsigned short* __restrict__ bias, const unsigned short* __restrict__ res,
+    const unsigned short* __restrict__ w, unsigned short* __restrict__ h_out,
+    unsigned short* __restrict__ n_out, long long MN, int D, int nsplit, float eps, float w_bias) {
+  __shared__ ushort8 hrow[8][256];  // the rounded h' row, [c][t]
+  __shared__ float red[4];
+  const int row = blockIdx.x;
+  const size_t off = (size_t)row * D;
+  const int t = threadIdx.x & 255, q = threadIdx.x >> 8;
+  float vals[8 / EPI_Q][8];
+#pragma unroll
+  for (int k = 0; k < 8 / EPI_Q; ++k) {
+    const int c = q + k * EPI_Q;
+    const int i = t * 8 + c * 256 * 8;
+    if (i < D) {
+      float yv[8];
+      if constexpr (PARTIALS) {
+        const float* p = P + off + i;
+        floatx4 s0 = *reinterpret_cast<const floatx4*>(p);
+        floatx4 s1 = *reinterpret_cast<const floatx4*>(p + 4);
+#pragma unroll 8
+        for (int sp = 1; sp < nsplit; ++sp) {
+          const floatx4 v0 = *reinterpret_cast<const floatx4*>(p + (size_t)sp * MN);
+          const floatx4 v1 = *reinterpret_cast<const floatx4*>(p + (size_t)sp * MN + 4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { s0[j] += v0[j]; s1[j] += v1[j]; }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { yv[j] = s0[j]; yv[4 + j] = s1[j]; }
+        if (bias) {
+          const ushort8 bv = *(const ushort8*)(bias + i);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) yv[j] += b2f(bv[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) yv[j] = b2f(f2b(yv[j]));
+      } else {
+        const ushort8 v = *(const ushort8*)(y + off + i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) yv[j] = b2f(v[j]);
+      }
+      const ushort8 r = *(const ushort8*)(res + off + i);
+      ushort8 s;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        s[j] = f2b(yv[j] + b2f(r[j]));
+        vals[k][j] = b2f(s[j]);
+      }
+      *(ushort8*)(h_out + off + i) = s;
+      hrow[c][t] = s;
+    }
+  }
+  if (w == nullptr) return;
+  __syncthreads();
+  if (q == 0) {
+    float acc = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (t * 8 + c * 256 * 8 < D) {
+        const ushort8 s = hrow[c][t];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float f = b2f(s[j]);
+          acc += f * f;
+        }
+      }
+    }
+    // wave reduce then cross-wave through LDS
+    acc = wave_sum(acc);
+    if ((t & 63) == 0) red[t >> 6] = acc;
+  }
+  __syncthreads();
+  const float total = red[0] + red[1] + red[2] + red[3];
+  const float inv = rsqrtf(total / (float)D + eps);
+#pragma unroll
+  for (int k = 0; k < 8 / EPI_Q; ++k) {
+    const int i = t * 8 + (q + k * EPI_Q) * 256 * 8;
+    if (i < D) {
+      ushort8 wv = *(const ushort8*)(w + i);
+      ushort8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = f2b(vals[k][j] * inv * (b2f(wv[j]) + w_bias));
+      *(ushort8*)(n_out + off + i) = o;
+    }
+  }
+}
+
 // ===========================================================================
 // host bindings
 // ===========================================================================
@@ -2293,15 +2477,20 @@ void rope_qkv_append(torch::Tensor qkv, torch::Tensor cos, torch::Tensor sin,
 struct SplitKV {
   torch::Tensor ws_o, ws_ml, out;
   int BH, nsplit, hd;
-  SplitKV(const torch::Tensor& q, at::IntArrayRef out_shape, int BH, int nsplit, int hd)
+  // workspace = false: the kernel merges in the workgroup and writes `out`
+  // itself — no partials are allocated and merge() is not called
+  SplitKV(const torch::Tensor& q, at::IntArrayRef out_shape, int BH, int nsplit, int hd,
+          bool workspace = true)
       : BH(BH), nsplit(nsplit), hd(hd) {
-    auto opts = torch::TensorOptions().dtype(torch::kFloat32).device(q.device());
-    ws_o = torch::empty({(long)BH * nsplit * hd}, opts);
-    ws_ml = torch::empty({(long)BH * nsplit * 2}, opts);
+    if (workspace) {
+      auto opts = torch::TensorOptions().dtype(torch::kFloat32).device(q.device());
+      ws_o = torch::empty({(long)BH * nsplit * hd}, opts);
+      ws_ml = torch::empty({(long)BH * nsplit * 2}, opts);
+    }
     out = torch::empty(out_shape, torch::TensorOptions().dtype(torch::kBFloat16).device(q.device()));
   }
-  float* o() const { return ws_o.data_ptr<float>(); }
-  float* ml() const { return ws_ml.data_ptr<float>(); }
+  float* o() const { return ws_o.defined() ? ws_o.data_ptr<float>() : nullptr; }
+  float* ml() const { return ws_ml.defined() ? ws_ml.data_ptr<float>() : nullptr; }
   torch::Tensor merge(hipStream_t stream) const {
     auto launch = [&](auto hdc) {
       constexpr int HD = decltype(hdc)::value;
@@ -2377,7 +2566,13 @@ torch::Tensor attn_decode_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor 
   // the packed-cache stream deep while chunks stay >= 32 positions
   int nsplit = 1;
   while (B * KVH * nsplit * 2 < 4096 && (T32 / (nsplit * 2)) >= 32 && nsplit < 32) nsplit *= 2;
-  const SplitKV kv(q, q.sizes(), B * H, nsplit, hd);
+  // nsplit in {1, 2, 4}: every split of a (b, kv-head) sits in one 4-wave
+  // workgroup, which then merges through LDS and writes the bf16 rows itself.
+  // XOT_ATTN_FUSED_MERGE=0 (read per call) keeps the workspace + merge launch.
+  const char* fm_env = getenv("XOT_ATTN_FUSED_MERGE");
+  const bool fused = (nsplit == 1 || nsplit == 2 || nsplit == 4) && H / KVH <= 16
+                     && ((fm_env == nullptr) || (fm_env[0] != '0'));
+  const SplitKV kv(q, q.sizes(), B * H, nsplit, hd, !fused);
   const float scale = (scale_in > 0.0) ? (float)scale_in : 1.0f / sqrtf((float)hd);
   auto stream = cur_stream();
   const int waves = B * KVH * nsplit;
@@ -2391,10 +2586,11 @@ torch::Tensor attn_decode_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor 
                          (const unsigned short*)q.data_ptr(), (const unsigned short*)kp.data_ptr(),
                          (const unsigned short*)vp.data_ptr(), seq_lens.data_ptr<int>(),
                          kv.o(), kv.ml(), B, H, KVH, T32, nsplit, scale, q_stride,
-                         (float)softcap, (int)window, skp, svp);
+                         (float)softcap, (int)window, skp, svp,
+                         fused ? (unsigned short*)kv.out.data_ptr() : nullptr);
     });
   });
-  return kv.merge(stream);
+  return fused ? kv.out : kv.merge(stream);
 }
 
 // q: [B, S, H, 128] (strided over b/s OK, head rows contiguous); kp/vp: the
@@ -2692,22 +2888,61 @@ struct SkinnyLaunch {
   int kc, nsplit;
 };
 
+// Optional row epilogue of a launcher (skinny_epilogue_kernel): the residual
+// to add and the norm that follows; run() fills h (= y + res) and, when a
+// norm weight is given, normed (= rmsnorm(h)).
+struct SkinnyEpilogue {
+  torch::Tensor res;
+  c10::optional<torch::Tensor> w;
+  double eps, w_bias;
+  torch::Tensor h, normed;
+
+  // exactly one of P (fp32 partials [nsplit, rows, D]) and y (bf16 [rows, D])
+  void run(const float* P, const unsigned short* y, const unsigned short* bias, long long rows,
+           long long D, int nsplit, hipStream_t stream) {
+    CHK(res.is_cuda() && res.dtype() == torch::kBFloat16 && res.is_contiguous());
+    CHK(res.numel() == rows * D && D % 8 == 0 && D <= 16384);
+    const unsigned short* wptr = nullptr;
+    h = torch::empty_like(res);
+    if (w.has_value()) {
+      CHK(w->is_cuda() && w->dtype() == torch::kBFloat16 && w->is_contiguous() && w->numel() == D);
+      wptr = (const unsigned short*)w->data_ptr();
+      normed = torch::empty_like(res);
+    }
+    dispatch_bool(P != nullptr, [&](auto partials) {
+      hipLaunchKernelGGL((skinny_epilogue_kernel<decltype(partials)::value>), dim3((unsigned)rows),
+                         dim3(EPI_Q * 256), 0, stream, P, y, bias, (const unsigned short*)res.data_ptr(), wptr,
+                         (unsigned short*)h.data_ptr(),
+                         wptr ? (unsigned short*)normed.data_ptr() : nullptr, rows * D, (int)D, nsplit,
+                         (float)eps, (float)w_bias);
+    });
+  }
+  std::vector<torch::Tensor> outputs() const {
+    return w.has_value() ? std::vector<torch::Tensor>{h, normed} : std::vector<torch::Tensor>{h};
+  }
+};
+
 // Shared tail of every launcher: validate bias, allocate y (and the fp32
 // partials P [nsplit, E*rows, N] when split), launch the kernel that
 // `launch(mt, split, bk, L)` names with MT / SPLIT / BK as compile-time
-// constants, then combine. rows = rows per expert.
+// constants, then combine. rows = rows per expert. With an epilogue the row
+// kernel takes the combine's place (split) or follows the GEMM's bf16 y
+// (unsplit); its results are left in *epi and the returned y is undefined
+// when split.
 template <bool HAS_BK128, class F>
 static torch::Tensor skinny_run(const torch::Tensor& x, at::IntArrayRef ysizes, long long rows,
                                 long long N, long long K, long long E,
-                                const c10::optional<torch::Tensor>& bias, int k_align, F&& launch) {
+                                const c10::optional<torch::Tensor>& bias, int k_align, F&& launch,
+                                SkinnyEpilogue* epi = nullptr) {
   const unsigned short* bptr = nullptr;
   if (bias.has_value()) {
     CHK(bias->is_contiguous() && bias->dtype() == torch::kBFloat16 && bias->numel() == N);
     bptr = (const unsigned short*)bias->data_ptr();
   }
-  auto y = torch::empty(ysizes, x.options().dtype(torch::kBFloat16));
   const SkinnyPlan p = skinny_plan(N, K, E, k_align, HAS_BK128);
   const bool is_split = p.nsplit > 1;
+  torch::Tensor y;
+  if (!(epi && is_split)) y = torch::empty(ysizes, x.options().dtype(torch::kBFloat16));
   torch::Tensor P;
   if (is_split)
     P = torch::empty({p.nsplit, (long)(E * rows), (long)N}, x.options().dtype(torch::kFloat32));
@@ -2724,7 +2959,10 @@ static torch::Tensor skinny_run(const torch::Tensor& x, at::IntArrayRef ysizes, 
     };
     if (is_split) with_split(std::true_type{}); else with_split(std::false_type{});
   });
-  if (is_split) {
+  if (epi) {
+    if (is_split) epi->run(P.data_ptr<float>(), nullptr, bptr, E * rows, N, p.nsplit, L.stream);
+    else epi->run(nullptr, (const unsigned short*)y.data_ptr(), nullptr, E * rows, N, 1, L.stream);
+  } else if (is_split) {
     const long long MN = E * rows * N;
     const int blocks = (int)std::min<long long>(2048, (MN / 4 + 255) / 256);
     hipLaunchKernelGGL(skinny_combine_kernel, dim3(blocks), dim3(256), 0, L.stream,
@@ -2757,8 +2995,9 @@ torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w,
 
 // Packed variant. wp: the [N/32, K/16, 64, 8] prepack of w (see
 // ops.pack_decode_weight), x: [M, K] bf16, M % 32 == 0, K % 64 == 0.
-torch::Tensor skinny_gemm_packed(torch::Tensor x, torch::Tensor wp, int64_t N,
-                                 c10::optional<torch::Tensor> bias) {
+static torch::Tensor skinny_gemm_packed_impl(const torch::Tensor& x, const torch::Tensor& wp, int64_t N,
+                                            const c10::optional<torch::Tensor>& bias,
+                                            SkinnyEpilogue* epi) {
   CHK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.is_contiguous());
   CHK(wp.is_cuda() && wp.dtype() == torch::kBFloat16 && wp.is_contiguous());
   const long long K = wp.numel() / N;
@@ -2773,7 +3012,24 @@ torch::Tensor skinny_gemm_packed(torch::Tensor x, torch::Tensor wp, int64_t N,
                        L.grid, dim3(256), 0, L.stream,
                        (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(),
                        L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit);
-  });
+  }, epi);
+}
+
+torch::Tensor skinny_gemm_packed(torch::Tensor x, torch::Tensor wp, int64_t N,
+                                 c10::optional<torch::Tensor> bias) {
+  return skinny_gemm_packed_impl(x, wp, N, bias, nullptr);
+}
+
+// skinny_gemm_packed + row epilogue: returns {h' = y + res} or, with a norm
+// weight, {h', rmsnorm(h')}; res: [M, N] bf16.
+std::vector<torch::Tensor> skinny_gemm_packed_epilogue(torch::Tensor x, torch::Tensor wp, int64_t N,
+                                                       c10::optional<torch::Tensor> bias,
+                                                       torch::Tensor res,
+                                                       c10::optional<torch::Tensor> norm_w,
+                                                       double eps, double w_bias) {
+  SkinnyEpilogue epi{res, norm_w, eps, w_bias};
+  skinny_gemm_packed_impl(x, wp, N, bias, &epi);
+  return epi.outputs();
 }
 
 // v3 (register-resident X) launcher — same contract as skinny_gemm_packed.
@@ -2800,8 +3056,9 @@ torch::Tensor skinny_gemm_packed_xreg(torch::Tensor x, torch::Tensor wp, int64_t
 // gate|up GEMM output, wp the prepacked down_proj ([N/32,K/16,64,8]);
 // computes y = (silu(gate) * up) @ W_down^T with the activation applied in
 // the X-staging — the intermediate [M, K] tensor never materializes.
-torch::Tensor skinny_gemm_packed_swiglu(torch::Tensor gu, torch::Tensor wp, int64_t N,
-                                        c10::optional<torch::Tensor> bias) {
+static torch::Tensor skinny_gemm_packed_swiglu_impl(const torch::Tensor& gu, const torch::Tensor& wp,
+                                                   int64_t N, const c10::optional<torch::Tensor>& bias,
+                                                   SkinnyEpilogue* epi) {
   CHK(gu.is_cuda() && gu.dtype() == torch::kBFloat16 && gu.is_contiguous());
   CHK(wp.is_cuda() && wp.dtype() == torch::kBFloat16 && wp.is_contiguous());
   const long long K = wp.numel() / N;
@@ -2818,7 +3075,35 @@ torch::Tensor skinny_gemm_packed_swiglu(torch::Tensor gu, torch::Tensor wp, int6
                        L.grid, dim3(256), 0, L.stream,
                        (const unsigned short*)wp.data_ptr(), (const unsigned short*)gu.data_ptr(),
                        L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit, ldx);
-  });
+  }, epi);
+}
+
+torch::Tensor skinny_gemm_packed_swiglu(torch::Tensor gu, torch::Tensor wp, int64_t N,
+                                        c10::optional<torch::Tensor> bias) {
+  return skinny_gemm_packed_swiglu_impl(gu, wp, N, bias, nullptr);
+}
+
+// skinny_gemm_packed_swiglu + row epilogue (see skinny_gemm_packed_epilogue)
+std::vector<torch::Tensor> skinny_gemm_packed_swiglu_epilogue(torch::Tensor gu, torch::Tensor wp, int64_t N,
+                                                              c10::optional<torch::Tensor> bias,
+                                                              torch::Tensor res,
+                                                              c10::optional<torch::Tensor> norm_w,
+                                                              double eps, double w_bias) {
+  SkinnyEpilogue epi{res, norm_w, eps, w_bias};
+  skinny_gemm_packed_swiglu_impl(gu, wp, N, bias, &epi);
+  return epi.outputs();
+}
+
+// h' = y + res and (with a norm weight) rmsnorm(h'), for a y that did not
+// come from a packed launcher (hipBLASLt, MoE); the rounding points of
+// torch add -> rmsnorm. y, res: bf16, same shape, contiguous.
+std::vector<torch::Tensor> add_rmsnorm(torch::Tensor y, torch::Tensor res,
+                                       c10::optional<torch::Tensor> norm_w, double eps, double w_bias) {
+  CHK(y.is_cuda() && y.dtype() == torch::kBFloat16 && y.is_contiguous() && y.numel() == res.numel());
+  const long long D = y.size(-1);
+  SkinnyEpilogue epi{res, norm_w, eps, w_bias};
+  epi.run(nullptr, (const unsigned short*)y.data_ptr(), nullptr, y.numel() / D, D, 1, cur_stream());
+  return epi.outputs();
 }
 
 // MoE grouped decode GEMM: x [E, C, K] (C = per-expert token capacity,
@@ -2895,6 +3180,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_packed", &skinny_gemm_packed,
         "decode GEMM on prepacked weights (MFMA fragment order)",
         py::arg("x"), py::arg("wp"), py::arg("n"), py::arg("bias") = py::none());
+  m.def("skinny_gemm_packed_epilogue", &skinny_gemm_packed_epilogue,
+        "skinny_gemm_packed + fused combine / residual add / following RMSNorm -> [h', normed]",
+        py::arg("x"), py::arg("wp"), py::arg("n"), py::arg("bias"), py::arg("res"),
+        py::arg("norm_w") = py::none(), py::arg("eps") = 1e-6, py::arg("w_bias") = 0.0);
+  m.def("skinny_gemm_packed_swiglu_epilogue", &skinny_gemm_packed_swiglu_epilogue,
+        "skinny_gemm_packed_swiglu + fused combine / residual add / following RMSNorm",
+        py::arg("gu"), py::arg("wp"), py::arg("n"), py::arg("bias"), py::arg("res"),
+        py::arg("norm_w") = py::none(), py::arg("eps") = 1e-6, py::arg("w_bias") = 0.0);
+  m.def("add_rmsnorm", &add_rmsnorm,
+        "h' = y + res and rmsnorm(h') of the rounded h' in one launch -> [h', normed]",
+        py::arg("y"), py::arg("res"), py::arg("norm_w") = py::none(), py::arg("eps") = 1e-6,
+        py::arg("w_bias") = 0.0);
   m.def("skinny_gemm_grouped", &skinny_gemm_grouped,
         "MoE grouped decode GEMM on stacked prepacked expert weights",
         py::arg("x"), py::arg("wp"), py::arg("n_experts"), py::arg("n"));

@@ -34,6 +34,17 @@ def rmsnorm_residual(
   return (norm * (weight.float() + w_bias)).to(x.dtype), s.to(x.dtype)
 
 
+def add_rmsnorm(
+  y: torch.Tensor, residual: torch.Tensor, weight: Optional[torch.Tensor], eps: float,
+  w_bias: float = 0.0
+) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+  """(h' = y + residual, rmsnorm(h')), rounding where the eager chain rounds:
+  h' to the input dtype first, the norm from that rounded h'. weight=None
+  gives (h', None)."""
+  h = y + residual
+  return h, (rmsnorm(h, weight, eps, w_bias) if weight is not None else None)
+
+
 def rope_cos_sin(
   head_dim: int,
   max_seq_len: int,
