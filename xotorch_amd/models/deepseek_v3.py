@@ -29,8 +29,10 @@ from typing import List
 import torch
 import torch.nn as nn
 
+from xotorch_amd import ops
 from xotorch_amd.models.config import ModelConfig
 from xotorch_amd.models.llama import XotLinear
+from xotorch_amd.models.moe import expert_loop, moe_decode, sorted_expert_prefill
 from xotorch_amd.ops.torch_ref import rope_cos_sin
 from xotorch_amd.shard import Shard
 
@@ -38,7 +40,6 @@ from xotorch_amd.shard import Shard
 def _rms(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
   if x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 \
      and x.shape[-1] % 8 == 0 and x.shape[-1] <= 16384:
-    from xotorch_amd import ops
     return ops.rmsnorm(x.contiguous(), w, eps)  # one HIP launch vs ~4 torch ops
   xf = x.float()
   out = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
@@ -297,7 +298,6 @@ class DsMoE(nn.Module):
     first = self.experts[0].gate_proj.weight
     if not (first.is_cuda and first.dtype == torch.bfloat16):
       return
-    from xotorch_amd import ops
     gu, dn = [], []
     for e in self.experts:
       w = torch.cat([e.gate_proj.weight.detach(), e.up_proj.weight.detach()], dim=0)
@@ -307,32 +307,15 @@ class DsMoE(nn.Module):
     self.wp_down = torch.stack(dn).contiguous()
 
   def _forward_decode(self, flat):
-    """Static-shape routed path (graph-capturable): sort token-expert pairs,
-    pad to a fixed per-expert capacity, one grouped MFMA launch per GEMM."""
-    from xotorch_amd import ops
-    from xotorch_amd.ops import _load_hip
-    hip = _load_hip()
-    cfg = self.cfg
-    T, D = flat.shape
-    E, k = cfg.n_experts, cfg.n_experts_per_tok
-    dev = flat.device
+    """Fused router, then the static-capacity pipeline (moe.moe_decode)."""
     cfg = self.cfg
     logits = nn.functional.linear(flat.float(), self.gate_weight.float())
-    idx, w = hip.moe_route(logits.contiguous(), self.e_score_correction_bias.float().contiguous(),
+    idx, w = ops.moe_route(logits.contiguous(), self.e_score_correction_bias.float().contiguous(),
                            cfg.n_experts_per_tok, 1, max(1, cfg.n_group),
                            max(1, cfg.topk_group), cfg.routed_scaling_factor,
                            bool(cfg.norm_topk_prob))
-    C = max(32, -(-T // 32) * 32)
-    # counting-sort routing + deterministic combine as single HIP launches
-    # (the torch glue — argsort/cumsum/index_add — was the measured top
-    # decode cost, profiles/r02_new_decoders_profile.md)
-    gather_tok, inv_pos = hip.moe_build(idx.to(torch.int32).contiguous(), E, C)
-    xg = flat[gather_tok.long()].to(flat.dtype)               # [E*C, D]
-    I = cfg.moe_intermediate_dim
-    gu = hip.skinny_gemm_grouped(xg.view(E, C, D).contiguous(), self.wp_gate_up, E, 2 * I)
-    h = ops.swiglu_packed(gu.view(E * C, 2 * I))
-    y = hip.skinny_gemm_grouped(h.view(E, C, I), self.wp_down, E, D).view(E * C, D)
-    return hip.moe_combine(y, inv_pos, w.float().contiguous())
+    return moe_decode(flat, idx, w, cfg.n_experts, cfg.moe_intermediate_dim, self.experts,
+                      self.wp_gate_up, self.wp_down)
 
   def forward(self, x):
     B, S, D = x.shape
@@ -348,35 +331,8 @@ class DsMoE(nn.Module):
         "model.pack_decode_weights() first (grouped static path), or bench "
         "with --no-graphs")
     idx, w = self.route(flat)
-    if x.is_cuda and not torch.is_grad_enabled():
-      # prefill: sorted contiguous per-expert slices (one argsort + gather
-      # instead of E where/eq scans)
-      k = self.cfg.n_experts_per_tok
-      dev = flat.device
-      expert_of = idx.reshape(-1)
-      order = torch.argsort(expert_of)
-      tok_sorted = torch.arange(T, device=dev).repeat_interleave(k)[order]
-      w_sorted = w.reshape(-1)[order]
-      counts = torch.bincount(expert_of, minlength=self.cfg.n_experts).cpu().tolist()
-      xg = flat[tok_sorted]
-      ys = []
-      off = 0
-      for e, c in enumerate(counts):
-        if c:
-          ys.append(self.experts[e](xg[off:off + c]))
-        off += c
-      y = torch.cat(ys, dim=0).float() * w_sorted[:, None].float()
-      out = torch.zeros(T, D, dtype=torch.float32, device=dev)
-      out.index_add_(0, tok_sorted, y)
-      out = out.to(x.dtype) + self.shared_experts(flat)
-      return out.view(B, S, D)
-    out = torch.zeros_like(flat, dtype=torch.float32)
-    for e in range(self.cfg.n_experts):
-      tok, kk = torch.where(idx == e)
-      if tok.numel() == 0:
-        continue
-      out.index_add_(0, tok, self.experts[e](flat[tok]).float() * w[tok, kk, None])
-    out = out.to(x.dtype) + self.shared_experts(flat)
+    run = sorted_expert_prefill if x.is_cuda and not torch.is_grad_enabled() else expert_loop
+    out = run(flat, w, idx, self.experts).to(x.dtype) + self.shared_experts(flat)
     return out.view(B, S, D)
 
 

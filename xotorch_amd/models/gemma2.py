@@ -33,7 +33,7 @@ import torch.nn as nn
 
 from xotorch_amd import ops
 from xotorch_amd.models.config import ModelConfig
-from xotorch_amd.models.llama import XotLinear
+from xotorch_amd.models.llama import XotLinear, pack_decode_weights
 from xotorch_amd.ops.torch_ref import rope_cos_sin
 from xotorch_amd.shard import Shard
 
@@ -231,10 +231,7 @@ class Gemma2Model(nn.Module):
     return list(range(self.shard.start_layer, self.shard.end_layer + 1))
 
   def pack_decode_weights(self, reserve_bytes: int = 8 << 30) -> int:
-    """Same greedy prepack policy as ShardedModel (descending measured-win
-    order, free-memory guarded)."""
-    from xotorch_amd.models.llama import ShardedModel
-    return ShardedModel.pack_decode_weights(self, reserve_bytes)
+    return pack_decode_weights(self, reserve_bytes)  # the policy ShardedModel uses
 
   def head_weight(self):
     if hasattr(self, "embed_tokens"):

@@ -24,171 +24,10 @@ import torch.nn as nn
 
 from xotorch_amd import ops
 from xotorch_amd.models.config import ModelConfig
+from xotorch_amd.models.linear import XotLinear, auto_pick, decode_rows
+from xotorch_amd.models.moe import expert_loop, moe_decode, sorted_expert_prefill
 from xotorch_amd.ops.torch_ref import rope_cos_sin
 from xotorch_amd.shard import Shard
-
-
-# (N, K, M) -> True when the packed skinny kernel beat hipBLASLt when timed
-# in-situ (first eligible call at that M, before hipGraph capture).
-_PACKED_WINS: dict = {}
-
-
-def _time_us(fn, reps=4, rounds=3) -> float:
-  """Min-of-rounds timing (DVFS / first-call noise makes a single round flip
-  borderline auto-picks between runs)."""
-  fn()  # warm
-  best = float("inf")
-  for _ in range(rounds):
-    start = torch.cuda.Event(enable_timing=True)
-    end = torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(reps):
-      fn()
-    end.record()
-    end.synchronize()
-    best = min(best, start.elapsed_time(end) * 1000.0 / reps)
-  return best
-
-
-def _packed_epilogue(fn, x, wp, N, bias, epilogue):
-  """Packed decode GEMM `fn` with its row epilogue -> (h', normed | None)."""
-  res, w, eps = epilogue
-  out = fn(x, wp, N, bias, res.contiguous(), w, eps, 0.0)
-  return out[0], (out[1] if w is not None else None)
-
-
-class XotLinear(nn.Linear):
-  """nn.Linear with an optional decode-path prepack: `pack_decode()` stores a
-  second copy of the weight in MFMA A-fragment order ([N/32,K/16,64,8], see
-  ops.pack_decode_weight); decode-shaped (rows 32..256) bf16 GEMMs then run
-  the hand-written CDNA4 weight-streaming kernel where it measures faster
-  than hipBLASLt (auto-picked per (N,K,M) at first call: e.g. 70B down_proj
-  110 -> 84.6 us, lm_head 5.3 -> 6.2 TB/s; hipBLASLt keeps the shapes it
-  wins). Prefill/training/CPU stay on hipBLASLt/aten. Storage/state-dict
-  identical to nn.Linear."""
-
-  weight_packed: Optional[torch.Tensor]
-
-  def __init__(self, *a, **kw):
-    super().__init__(*a, **kw)
-    self.weight_packed = None
-    self.weight_packed_fp8 = None
-    self.weight_scale = None
-
-  def packable(self) -> bool:
-    N, K = self.weight.shape
-    return N % 128 == 0 and K % 64 == 0
-
-  def pack_decode(self):
-    if self.packable() and self.weight.is_cuda and self.weight.dtype == torch.bfloat16:
-      if ops.fp8_gemm_enabled():
-        if getattr(self, "weight_packed_fp8", None) is None:
-          self.weight_packed_fp8, self.weight_scale = ops.pack_decode_weight_fp8(self.weight.detach())
-      elif self.weight_packed is None:
-        self.weight_packed = ops.pack_decode_weight(self.weight.detach())
-
-  def unpack_decode(self):
-    self.weight_packed = None
-    self.weight_packed_fp8 = None
-
-  _w8 = None
-  _w8_scale = None
-
-  def _fp8_prefill(self, x):
-    """Opt-in (XOT_FP8_PREFILL=1) e4m3 prefill GEMM via hipBLASLt scaled_mm:
-    measured 2.58 vs 1.58 PF on the 70B gate_up prefill shape (rel err
-    ~3.5%). Per-token activation scales, per-channel weight scales; the
-    fp8 weight copy is cached lazily."""
-    N, K = self.weight.shape
-    M = x.numel() // K
-    w8, sw = self._w8, self._w8_scale
-    if w8 is None:
-      w = self.weight.detach()
-      sw = (w.float().abs().amax(dim=1, keepdim=True).clamp(min=1e-12) / 448.0)
-      w8 = (w / sw.to(w.dtype)).clamp(-448, 448).to(torch.float8_e4m3fn)
-      free, _ = torch.cuda.mem_get_info()
-      if free > (12 << 30):  # persist the fp8 copy only with HBM headroom
-        self._w8, self._w8_scale = w8, sw
-    # activation quantization stays in bf16 (a fp32 image of a 65k x 8k
-    # prefill activation would be 2 GB per layer)
-    x2 = x.reshape(M, K)
-    sx = (x2.abs().amax(dim=1, keepdim=True).float().clamp(min=1e-12) / 448.0)
-    x8 = (x2 / sx.to(x2.dtype)).clamp(-448, 448).to(torch.float8_e4m3fn)
-    y = torch._scaled_mm(x8, w8.t(), scale_a=sx, scale_b=sw.t(),
-                         out_dtype=torch.bfloat16)
-    if self.bias is not None:
-      y = y + self.bias
-    return y.view(list(x.shape[:-1]) + [N])
-
-  def forward(self, x, epilogue=None):
-    """epilogue = (residual, norm_weight | None, eps) turns the result into
-    (h' = y + residual, rmsnorm(h') | None): inside the packed kernel's
-    split-K combine where that path is picked, else one add_rmsnorm launch."""
-    y = self._gemm(x, epilogue)
-    if epilogue is None or isinstance(y, tuple):
-      return y
-    res, w, eps = epilogue
-    return ops.add_rmsnorm(y, res.view(y.shape), w, eps)
-
-  def _gemm(self, x, epilogue=None):
-    if (x.is_cuda and x.dtype == torch.bfloat16 and not torch.is_grad_enabled()
-        and os.getenv("XOT_FP8_PREFILL", "0") == "1"):
-      N, K = self.weight.shape
-      M = x.numel() // K
-      if M > 256 and N % 16 == 0 and K % 16 == 0 and x.is_contiguous():
-        try:
-          return self._fp8_prefill(x)
-        except torch.cuda.OutOfMemoryError:
-          torch.cuda.empty_cache()  # fall back to the bf16 path
-    wp8 = getattr(self, "weight_packed_fp8", None)
-    if wp8 is not None and x.is_cuda and x.dtype == torch.bfloat16 and not torch.is_grad_enabled():
-      N, K = self.weight.shape
-      M = x.numel() // K
-      if 32 <= M <= 256 and M % 32 == 0 and x.is_contiguous():
-        from xotorch_amd.ops import _load_hip
-        hip = _load_hip()
-        if hip is not None:
-          x8, sx = hip.quant_fp8_rows(x.view(M, K))
-          y = hip.skinny_gemm_fp8(x8, sx, wp8, self.weight_scale, 1, N, self.bias)
-          sizes = list(x.shape[:-1]) + [N]
-          return y.view(sizes)
-    if self.weight_packed is not None and x.is_cuda and x.dtype == torch.bfloat16:
-      N, K = self.weight.shape
-      M = x.numel() // K
-      if 32 <= M <= 256 and M % 32 == 0 and x.is_contiguous() and not torch.is_grad_enabled():
-        from xotorch_amd.ops import _load_hip
-        hip = _load_hip()
-        if hip is not None:
-          key = (N, K, M)
-          use = _PACKED_WINS.get(key)
-          if use is None:
-            if torch.cuda.is_current_stream_capturing():
-              use = "packed"  # no timing under capture; normal warmup decides first
-            else:
-              wp, w, b = self.weight_packed, self.weight, self.bias
-              t_packed = _time_us(lambda: hip.skinny_gemm_packed(x, wp, N, b))
-              t_xreg = _time_us(lambda: hip.skinny_gemm_packed_xreg(x, wp, N, b))
-              t_blaslt = _time_us(lambda: torch.nn.functional.linear(x, w, b))
-              # require a clear (>5%) win over hipBLASLt: real wins measure
-              # 20%+ and borderline shapes would flip run-to-run with DVFS
-              use = "blaslt"
-              t_best = t_blaslt * 0.95
-              if t_packed < t_best:
-                use, t_best = "packed", t_packed
-              if t_xreg < t_best:
-                use = "xreg"
-              _PACKED_WINS[key] = use
-              if os.getenv("XOT_DEBUG", "0") != "0":
-                print(f"[xot] gemm auto-pick N={N} K={K} M={M}: packed {t_packed:.1f} us "
-                      f"/ xreg {t_xreg:.1f} us vs blaslt {t_blaslt:.1f} us -> {use}", flush=True)
-          if use == "xreg":
-            return hip.skinny_gemm_packed_xreg(x, self.weight_packed, N, self.bias)
-          if use == "packed":
-            if epilogue is not None:
-              return _packed_epilogue(hip.skinny_gemm_packed_epilogue, x, self.weight_packed, N,
-                                      self.bias, epilogue)
-            return hip.skinny_gemm_packed(x, self.weight_packed, N, self.bias)
-    return ops.linear(x, self.weight, self.bias)
 
 
 class RMSNorm(nn.Module):
@@ -283,53 +122,31 @@ class MLP(nn.Module):
   def forward(self, x, epilogue=None):
     """epilogue: see XotLinear.forward — the down projection carries it."""
     gu = self.gate_up_proj(x)
-    dp = self.down_proj
-    if (getattr(dp, "weight_packed", None) is not None and gu.is_cuda and gu.dtype == torch.bfloat16
-        and not torch.is_grad_enabled() and gu.is_contiguous()
-        and os.getenv("XOT_FUSE_SWIGLU", "1") == "1"):
-      I = self.intermediate
-      M = gu.numel() // (2 * I)
-      if 32 <= M <= 256 and M % 32 == 0:
-        from xotorch_amd.ops import _load_hip
-        hip = _load_hip()
-        if hip is not None:
-          N = dp.weight.shape[0]
-          key = ("fuse_swiglu", N, I, M)
-          use = _PACKED_WINS.get(key)
-          if use is None:
-            if torch.cuda.is_current_stream_capturing():
-              use = "fused"
-            else:
-              wp = dp.weight_packed
-              t_fused = _time_us(lambda: hip.skinny_gemm_packed_swiglu(gu, wp, N, dp.bias))
-              t_split = _time_us(lambda: dp(ops.swiglu_packed(gu)))
-              use = "fused" if t_fused < t_split * 0.98 else "split"
-              _PACKED_WINS[key] = use
-              if os.getenv("XOT_DEBUG", "0") != "0":
-                print(f"[xot] swiglu-fuse auto-pick N={N} I={I} M={M}: fused {t_fused:.1f} us "
-                      f"vs split {t_split:.1f} us -> {use}", flush=True)
-          if use == "fused":
-            if epilogue is not None:
-              return _packed_epilogue(hip.skinny_gemm_packed_swiglu_epilogue, gu, dp.weight_packed,
-                                      N, dp.bias, epilogue)
-            y = hip.skinny_gemm_packed_swiglu(gu, dp.weight_packed, N, dp.bias)
-            return y.view(list(x.shape[:-1]) + [N])
-    if epilogue is not None:
-      return self.down_proj(ops.swiglu_packed(gu), epilogue)
-    return self.down_proj(ops.swiglu_packed(gu))
+    dp, I = self.down_proj, self.intermediate
+    wp = getattr(dp, "weight_packed", None)  # dp may be a LoRA wrapper (train/lora.py)
+    if wp is not None and os.getenv("XOT_FUSE_SWIGLU", "1") == "1":
+      M = decode_rows(gu, 2 * I)
+      if M:
+        N = dp.weight.shape[0]
+        use = auto_pick(("fuse_swiglu", N, I, M), "swiglu-fuse", "NIM", 0.98, lambda: [
+          ("split", lambda: dp(ops.swiglu_packed(gu))),
+          ("fused", lambda: ops.skinny_gemm_packed_swiglu(gu, wp, N, dp.bias))])
+        if use == "fused":
+          if epilogue is not None:
+            return ops.skinny_gemm_packed_swiglu_epilogue(gu, wp, N, dp.bias, epilogue)
+          return ops.skinny_gemm_packed_swiglu(gu, wp, N, dp.bias).view(list(x.shape[:-1]) + [N])
+    h = ops.swiglu_packed(gu)
+    return dp(h) if epilogue is None else dp(h, epilogue)  # a LoRA wrapper takes x alone
 
 
 class MoEMLP(nn.Module):
   """Mixtral-class sparse MoE block (top-k routed SwiGLU experts).
 
-  Decode (<=256 tokens, GPU inference) runs a STATIC-SHAPE routed path that
-  is hipGraph-capturable: assignments are argsorted by expert, every expert
-  gets a fixed token capacity C = round_up(T, 32) (top-k experts are distinct
-  per token so a single expert can receive at most T assignments — lossless),
-  padded slots carry weight 0, and the per-expert GEMMs run as ONE grouped
-  MFMA launch on stacked prepacked weights (`skinny_gemm_grouped`) when
-  packed, else per-expert XotLinear. Prefill/CPU/training use the dynamic
-  gather loop (the reference's semantics, llm_utils.py:502-590)."""
+  Decode (<=256 tokens, GPU inference) runs the STATIC-SHAPE, hipGraph-
+  capturable routed path (moe.moe_decode): ONE grouped MFMA launch per expert
+  GEMM on stacked prepacked weights when packed, else per-expert XotLinear.
+  Prefill/CPU/training use the dynamic gather loop (the reference's
+  semantics, llm_utils.py:502-590)."""
 
   def __init__(self, cfg: ModelConfig):
     super().__init__()
@@ -387,107 +204,23 @@ class MoEMLP(nn.Module):
     # prefill was measured 1.5-2.5x WORSE TTFT (every chunk re-streams the
     # full expert weights; the eager loop streams each expert once with a
     # large-M GEMM). Instead, prefill sorts the token-expert pairs ONCE and
-    # runs each expert on a contiguous slice — one argsort + one gather
-    # replaces E per-expert where/eq scans over the full assignment list.
+    # runs each expert on a contiguous slice (moe.sorted_expert_prefill).
     weights, selected = self._route(flat)
-    if x.is_cuda and not torch.is_grad_enabled():
-      return self._forward_prefill_sorted(flat, weights, selected).view(B, S, D).to(x.dtype)
-    out = torch.zeros_like(flat, dtype=torch.float32)
-    for e in range(self.n_experts):
-      token_idx, k_idx = torch.where(selected == e)
-      if token_idx.numel() == 0:
-        continue
-      expert_out = self.experts[e](flat[token_idx]).float()
-      out.index_add_(0, token_idx, expert_out * weights[token_idx, k_idx, None])
-    return out.view(B, S, D).to(x.dtype)
-
-  def _forward_prefill_sorted(self, flat, weights, selected):
-    T, D = flat.shape
-    k = self.top_k
-    A = T * k
-    dev = flat.device
-    expert_of = selected.reshape(-1)
-    order = torch.argsort(expert_of)
-    tok_sorted = torch.arange(T, device=dev).repeat_interleave(k)[order]
-    w_sorted = weights.reshape(-1)[order]
-    counts = torch.bincount(expert_of, minlength=self.n_experts).cpu().tolist()  # one sync
-    xg = flat[tok_sorted]
-    ys = []
-    off = 0
-    for e, c in enumerate(counts):
-      if c:
-        ys.append(self.experts[e](xg[off:off + c]))
-      off += c
-    y = torch.cat(ys, dim=0).float() * w_sorted[:, None].float()
-    out = torch.zeros(T, D, dtype=torch.float32, device=dev)
-    out.index_add_(0, tok_sorted, y)
-    return out
+    run = sorted_expert_prefill if x.is_cuda and not torch.is_grad_enabled() else expert_loop
+    return run(flat, weights, selected, self.experts).view(B, S, D).to(x.dtype)
 
   def _forward_decode(self, flat):
-    T, D = flat.shape
-    E, k = self.n_experts, self.top_k
-    dev = flat.device
-    from xotorch_amd.ops import _load_hip
-    hip0 = _load_hip()
-    C = max(32, -(-T // 32) * 32)                             # capacity (lossless: count_e <= T)
-    if hip0 is not None and flat.is_cuda:
+    """Routing, then the static-capacity pipeline (moe.moe_decode)."""
+    if flat.is_cuda and ops.hip_available():
       # fused router (softmax-topk-renorm in one launch)
-      logits = self.gate(flat).float()
-      selected, weights = hip0.moe_route(logits.contiguous(), None, self.top_k, 0)
+      selected, weights = ops.moe_route(self.gate(flat).float().contiguous(), None, self.top_k, 0)
     else:
       weights, selected = self._route(flat)                   # [T, k]
-    if hip0 is not None and flat.is_cuda:
-      # single-launch counting-sort + deterministic combine (replaces the
-      # argsort/cumsum/index_add torch glue — measured top MoE decode cost)
-      gather_tok, inv_pos = hip0.moe_build(selected.to(torch.int32).contiguous(), E, C)
-      gather_tok = gather_tok.long()
-      scale = None
+    if self.wp_gate_up_fp8 is not None:
+      packs = (self.wp_gate_up_fp8, self.wp_down_fp8, (self.sw_gate_up, self.sw_down))
     else:
-      A = T * k
-      expert_of = selected.reshape(A)                         # [A]
-      token_of = torch.arange(T, device=dev).repeat_interleave(k)
-      w_of = weights.reshape(A)
-      order = torch.argsort(expert_of)                        # static shape [A]
-      sorted_token = token_of[order]
-      sorted_w = w_of[order]
-      counts = (expert_of.unsqueeze(0) == torch.arange(E, device=dev).unsqueeze(1)).sum(1)
-      offsets = torch.cumsum(counts, 0) - counts              # exclusive prefix
-      c_idx = torch.arange(C, device=dev)
-      pos = offsets.unsqueeze(1) + c_idx.unsqueeze(0)         # [E, C]
-      valid = c_idx.unsqueeze(0) < counts.unsqueeze(1)
-      pos_c = pos.clamp(max=A - 1)
-      gather_tok = sorted_token[pos_c.reshape(-1)]            # [E*C]
-      scale = torch.where(valid, sorted_w[pos_c], torch.zeros((), dtype=sorted_w.dtype, device=dev))
-    xg = flat[gather_tok]                                     # [E*C, D]
-    if self.wp_gate_up_fp8 is not None and not torch.is_grad_enabled():
-      from xotorch_amd.ops import _load_hip
-      hip = _load_hip()
-      I = self.intermediate
-      x8, sx = hip.quant_fp8_rows(xg)
-      gu = hip.skinny_gemm_fp8(x8, sx, self.wp_gate_up_fp8, self.sw_gate_up.view(-1), E, 2 * I)
-      h = ops.swiglu_packed(gu.view(E * C, 2 * I))
-      h8, sh = hip.quant_fp8_rows(h)
-      y = hip.skinny_gemm_fp8(h8, sh, self.wp_down_fp8, self.sw_down.view(-1), E, D)
-      y = y.view(E * C, D)
-    elif self.wp_gate_up is not None and not torch.is_grad_enabled():
-      from xotorch_amd.ops import _load_hip
-      hip = _load_hip()
-      gu = hip.skinny_gemm_grouped(xg.view(E, C, D), self.wp_gate_up, E, 2 * self.intermediate)
-      h = ops.swiglu_packed(gu.view(E * C, 2 * self.intermediate))
-      y = hip.skinny_gemm_grouped(h.view(E, C, self.intermediate), self.wp_down, E, D)
-      y = y.view(E * C, D)
-    else:
-      xe = xg.view(E, C, D)
-      outs = []
-      for e in range(E):
-        outs.append(self.experts[e](xe[e]))
-      y = torch.cat(outs, dim=0)
-    if scale is None:
-      return hip0.moe_combine(y.view(E * C, D).to(torch.bfloat16).contiguous(), inv_pos,
-                              weights.float().contiguous()).float()
-    out = torch.zeros(T, D, dtype=torch.float32, device=dev)
-    out.index_add_(0, gather_tok, y.float() * scale.reshape(-1, 1))
-    return out
+      packs = (self.wp_gate_up, self.wp_down)
+    return moe_decode(flat, selected, weights, self.n_experts, self.intermediate, self.experts, *packs)
 
 
 class DecoderLayer(nn.Module):
@@ -522,6 +255,63 @@ class DecoderLayer(nn.Module):
     if isinstance(self.mlp, MLP):
       return self.mlp(normed, epilogue)
     return ops.add_rmsnorm(self.mlp(normed), h, next_norm_w, self.eps)
+
+
+def pack_decode_weights(model, reserve_bytes: int) -> int:
+  """Prepack decode-GEMM weights (second copy in MFMA fragment order) in
+  descending measured-win order — down_proj (hipBLASLt ~3 TB/s at K=28672
+  vs 5.4 packed), lm_head, gate_up, qkv/o — greedily while at least
+  `reserve_bytes` of HBM stay free (KV caches and activations are usually
+  allocated before this is called). Returns bytes packed. Policy override:
+  XOT_PACK=none|down|all."""
+  mode = os.getenv("XOT_PACK", "auto")
+  if mode == "none" or not torch.cuda.is_available():
+    return 0
+  groups: List[List[XotLinear]] = [[], [], [], []]
+  for name, mod in model.named_modules():
+    if not isinstance(mod, XotLinear) or not mod.packable():
+      continue
+    if "down_proj" in name:
+      # the packed kernel wins when the split-K grid still fills the chip
+      # (>= ~1.5 blocks/CU); small-N down projections stay on hipBLASLt.
+      # MoE experts always pack: the grouped launch fills via blockIdx.y.
+      if "experts." in name or mod.weight.shape[0] // 128 * 8 >= 384 or mode == "all":
+        groups[0].append(mod)
+    elif "lm_head" in name:
+      groups[1].append(mod)
+    elif "gate_up_proj" in name:
+      groups[2].append(mod)
+    else:  # qkv_proj / o_proj / experts' projections
+      groups[3].append(mod)
+  if mode != "all" and not ops.fp8_gemm_enabled():
+    # default (bf16): the measured winners — down_proj (tuned hipBLASLt
+    # 110 us vs 84.6 packed at 70B decode shapes), lm_head (5.3 -> 6.2
+    # TB/s), gate_up (175.5 vs 178.9 us); qkv/o measure tied on hipBLASLt
+    # — not worth the second weight copy. In fp8 mode every group wins
+    # (half the stream bytes), so all are packed.
+    groups = groups[:3]
+  packed = 0
+  debug = os.getenv("XOT_DEBUG", "0") != "0"
+  for gi, grp in enumerate(groups):
+    if not grp:
+      continue
+    bytes_per = 1 if ops.fp8_gemm_enabled() else 2
+    need = sum(m.weight.numel() * bytes_per for m in grp)
+    free, _ = torch.cuda.mem_get_info()
+    if need + reserve_bytes > free:
+      if debug:
+        print(f"[xot] pack group {gi}: skip (need {need>>20} MiB + reserve "
+              f"{reserve_bytes>>20} MiB > free {free>>20} MiB)", flush=True)
+      continue
+    for m in grp:
+      m.pack_decode()
+    packed += need
+    if debug:
+      print(f"[xot] pack group {gi}: packed {len(grp)} modules, {need>>20} MiB", flush=True)
+  for mod in model.modules():
+    if isinstance(mod, MoEMLP):
+      mod.pack_grouped()
+  return packed
 
 
 class ShardedModel(nn.Module):
@@ -567,60 +357,7 @@ class ShardedModel(nn.Module):
     return list(range(self.shard.start_layer, self.shard.end_layer + 1))
 
   def pack_decode_weights(self, reserve_bytes: int = 8 << 30) -> int:
-    """Prepack decode-GEMM weights (second copy in MFMA fragment order) in
-    descending measured-win order — down_proj (hipBLASLt ~3 TB/s at K=28672
-    vs 5.4 packed), lm_head, gate_up, qkv/o — greedily while at least
-    `reserve_bytes` of HBM stay free (KV caches and activations are usually
-    allocated before this is called). Returns bytes packed. Policy override:
-    XOT_PACK=none|down|all."""
-    mode = os.getenv("XOT_PACK", "auto")
-    if mode == "none" or not torch.cuda.is_available():
-      return 0
-    groups: List[List[XotLinear]] = [[], [], [], []]
-    for name, mod in self.named_modules():
-      if not isinstance(mod, XotLinear) or not mod.packable():
-        continue
-      if "down_proj" in name:
-        # the packed kernel wins when the split-K grid still fills the chip
-        # (>= ~1.5 blocks/CU); small-N down projections stay on hipBLASLt.
-        # MoE experts always pack: the grouped launch fills via blockIdx.y.
-        if "experts." in name or mod.weight.shape[0] // 128 * 8 >= 384 or mode == "all":
-          groups[0].append(mod)
-      elif "lm_head" in name:
-        groups[1].append(mod)
-      elif "gate_up_proj" in name:
-        groups[2].append(mod)
-      else:  # qkv_proj / o_proj / experts' projections
-        groups[3].append(mod)
-    if mode != "all" and not ops.fp8_gemm_enabled():
-      # default (bf16): the measured winners — down_proj (tuned hipBLASLt
-      # 110 us vs 84.6 packed at 70B decode shapes), lm_head (5.3 -> 6.2
-      # TB/s), gate_up (175.5 vs 178.9 us); qkv/o measure tied on hipBLASLt
-      # — not worth the second weight copy. In fp8 mode every group wins
-      # (half the stream bytes), so all are packed.
-      groups = groups[:3]
-    packed = 0
-    debug = os.getenv("XOT_DEBUG", "0") != "0"
-    for gi, grp in enumerate(groups):
-      if not grp:
-        continue
-      bytes_per = 1 if ops.fp8_gemm_enabled() else 2
-      need = sum(m.weight.numel() * bytes_per for m in grp)
-      free, _ = torch.cuda.mem_get_info()
-      if need + reserve_bytes > free:
-        if debug:
-          print(f"[xot] pack group {gi}: skip (need {need>>20} MiB + reserve "
-                f"{reserve_bytes>>20} MiB > free {free>>20} MiB)", flush=True)
-        continue
-      for m in grp:
-        m.pack_decode()
-      packed += need
-      if debug:
-        print(f"[xot] pack group {gi}: packed {len(grp)} modules, {need>>20} MiB", flush=True)
-    for mod in self.modules():
-      if isinstance(mod, MoEMLP):
-        mod.pack_grouped()
-    return packed
+    return pack_decode_weights(self, reserve_bytes)
 
   def head_weight(self):
     if self.cfg.tie_word_embeddings and hasattr(self, "embed_tokens"):

@@ -183,7 +183,48 @@ def geglu_packed(gu):
   return torch_ref.geglu_packed(gu)
 
 
-_SKINNY = os.getenv("XOT_SKINNY", "1") == "1"
+# ---- GPU-only bindings: the decode GEMMs on prepacked weights (x [.., K]
+# bf16, 32..256 rows in multiples of 32; wp from pack_decode_weight[_fp8]) and
+# the MoE decode launches. No torch twin: models/linear.py and models/moe.py
+# decide when they run, and a missing extension is an error.
+
+def _gpu():
+  if _load_hip() is None:
+    raise RuntimeError(f"xotorch_amd HIP extension is not built (load error: {_hip_load_error})")
+  return _hip
+
+
+def _binding(name: str):
+  return lambda *args: getattr(_gpu(), name)(*args)
+
+
+skinny_gemm_packed = _binding("skinny_gemm_packed")                # (x, wp, N, bias) -> [.., N]
+skinny_gemm_packed_xreg = _binding("skinny_gemm_packed_xreg")      # the same, x held in registers
+skinny_gemm_packed_swiglu = _binding("skinny_gemm_packed_swiglu")  # (gu [.., 2I], wp, N, bias): swiglu + GEMM
+skinny_gemm_grouped = _binding("skinny_gemm_grouped")  # (x [E, C, K], stacked wp, E, N) -> [E, C, N]
+quant_fp8_rows = _binding("quant_fp8_rows")            # (x [M, K]) -> (e4m3 bytes [M, K], fp32 row scales [M])
+skinny_gemm_fp8 = _binding("skinny_gemm_fp8")          # (x8, sx, wp8, sw, E, N[, bias]): W8A8, grouped when E > 1
+# (fp32 logits [T, E], bias | None, k, mode[, n_group, topk_group, routed_scale, norm_topk]) -> (ids [T, k]
+# int32, weights [T, k] fp32); mode 0 softmax-topk-renorm, mode 1 sigmoid + group-limited top-k
+moe_route = _binding("moe_route")
+moe_build = _binding("moe_build")      # (ids int32 [T, k], E, C): counting sort -> (gather_tok [E*C], inv_pos [T, k])
+moe_combine = _binding("moe_combine")  # (y [E*C, D], inv_pos, weights fp32) -> [T, D] bf16, deterministic
+
+
+def _packed_epilogue(fn, x, wp, N, bias, epilogue):
+  """Packed decode GEMM `fn` with its row epilogue (residual, norm_weight |
+  None, eps) -> (h' = y + residual, rmsnorm(h') | None)."""
+  res, w, eps = epilogue
+  out = fn(x, wp, N, bias, res.contiguous(), w, eps, 0.0)
+  return out[0], (out[1] if w is not None else None)
+
+
+def skinny_gemm_packed_epilogue(x, wp, N: int, bias, epilogue):
+  return _packed_epilogue(_gpu().skinny_gemm_packed_epilogue, x, wp, N, bias, epilogue)
+
+
+def skinny_gemm_packed_swiglu_epilogue(gu, wp, N: int, bias, epilogue):
+  return _packed_epilogue(_gpu().skinny_gemm_packed_swiglu_epilogue, gu, wp, N, bias, epilogue)
 
 
 def pack_decode_weight(w: torch.Tensor) -> torch.Tensor:
