@@ -177,8 +177,7 @@ def test_gemma2_per_row_positions():
   toks = torch.randint(0, cfg.vocab_size, (B, 10))
   with torch.inference_mode():
     for b, L in enumerate(lens):
-      sliced = [tuple(t[b:b + 1] if t is not None else None for t in layer) for layer in cache.caches]
-      m(toks[b:b + 1, :L], caches=sliced, positions=torch.arange(L), start_pos=0)
+      m(toks[b:b + 1, :L], caches=cache.rows(b, b + 1), positions=torch.arange(L), start_pos=0)
     nxt = toks[:, :1]
     refs = []
     for b, L in enumerate(lens):

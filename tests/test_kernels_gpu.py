@@ -911,12 +911,8 @@ def test_fp8_kv_append_and_decode(hip):
   assert err < 0.12 * max(scale_ref, 1.0) + 0.05, (err, scale_ref)
 
 
-@pytest.mark.gpu
-def test_fp8_kv_end_to_end_model(monkeypatch):
-  """XOT_FP8_KV=1 end to end on a tiny hd=128 llama: argmax agreement with
-  the bf16-cache run."""
-  monkeypatch.setenv("XOT_FP8_KV", "1")
-  from xotorch_amd.engine.kvcache import ShardKVCache
+def _fp8kv_tiny_model():
+  """The tiny hd=128, 2-layer llama of the fp8-KV end-to-end tests."""
   from xotorch_amd.models.config import config_from_hf
   from xotorch_amd.models.llama import ShardedModel
   from xotorch_amd.models.weights import random_init
@@ -932,6 +928,60 @@ def test_fp8_kv_end_to_end_model(monkeypatch):
   random_init(m)
   m.reset_rope()
   m.eval()
+  return m
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fp8_kv", ["1", "0"])
+def test_row_chunked_prefill_keeps_every_cache_field(monkeypatch, fp8_kv):
+  """Prefill in two row chunks through ShardKVCache.rows() (what the ring
+  does above XOT_PREFILL_CHUNK) equals, bit for bit, the same chunks through
+  hand-sliced 6-tuples: logits and all six cache tensors, fp8 scales
+  included. One whole-batch decode step then agrees with the bf16-KV cache
+  as test_fp8_kv_end_to_end_model asks. S=33 crosses a 32-position tile and
+  leaves a ragged 16-tile."""
+  from xotorch_amd.engine.kvcache import ShardKVCache
+  m = _fp8kv_tiny_model()
+  B, S = 4, 33
+  toks = torch.randint(0, 512, (B, S), device="cuda")
+  monkeypatch.setenv("XOT_FP8_KV", fp8_kv)
+  by_rows = ShardKVCache(2, B, 2, S + 8, 128, torch.bfloat16, "cuda")
+  by_hand = ShardKVCache(2, B, 2, S + 8, 128, torch.bfloat16, "cuda")
+  assert (by_rows.caches[0].ksc is not None) == (fp8_kv == "1")
+  monkeypatch.setenv("XOT_FP8_KV", "0")
+  bf16 = ShardKVCache(2, B, 2, S + 8, 128, torch.bfloat16, "cuda")
+  pos = torch.arange(S, dtype=torch.int32, device="cuda")
+
+  def hand(cache, b0, b1):
+    return [tuple(t[b0:b1] if t is not None else None for t in layer) for layer in cache.caches]
+
+  with torch.inference_mode():
+    l_rows, l_hand, l_bf16 = (
+      torch.cat([m(toks[b0:b1], caches=slicer(b0, b1), positions=pos, start_pos=0)
+                 for b0, b1 in ((0, 2), (2, 4))])
+      for slicer in (by_rows.rows, lambda b0, b1: hand(by_hand, b0, b1), bf16.rows))
+    assert torch.equal(l_rows, l_hand)
+    for la, lb in zip(by_rows.caches, by_hand.caches):
+      for name, ta, tb in zip(la._fields, la, lb):
+        assert (ta is None and tb is None) or torch.equal(ta, tb), name
+    assert (l_rows.argmax(-1) == l_bf16.argmax(-1)).all()  # prefill identical (plain cache)
+    nxt = l_bf16.argmax(-1, keepdim=True)
+    sl = torch.full((B,), S + 1, dtype=torch.int32, device="cuda")
+    p1 = torch.tensor([S], dtype=torch.int32, device="cuda")
+    d = m(nxt, caches=by_rows.caches, positions=p1, start_pos=S, is_decode=True, seq_lens=sl)
+    db = m(nxt, caches=bf16.caches, positions=p1, start_pos=S, is_decode=True, seq_lens=sl)
+    assert torch.isfinite(d.float()).all()
+    assert torch.allclose(d.float(), db.float(), atol=0.5, rtol=0.1), \
+      (d.float() - db.float()).abs().max()
+
+
+@pytest.mark.gpu
+def test_fp8_kv_end_to_end_model(monkeypatch):
+  """XOT_FP8_KV=1 end to end on a tiny hd=128 llama: argmax agreement with
+  the bf16-cache run."""
+  monkeypatch.setenv("XOT_FP8_KV", "1")
+  from xotorch_amd.engine.kvcache import ShardKVCache
+  m = _fp8kv_tiny_model()
   B, S = 2, 24
   toks = torch.randint(0, 512, (B, S), device="cuda")
   c8 = ShardKVCache(2, B, 2, S + 8, 128, torch.bfloat16, "cuda")

@@ -5,10 +5,9 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
 
+from xotorch_amd.models.build import build_shard_model
 from xotorch_amd.models.config import config_from_hf
 from xotorch_amd.models.registry import builtin_config
-from xotorch_amd.models.llama import ShardedModel
-from xotorch_amd.models.weights import fast_random_init_gpu
 from xotorch_amd.shard import Shard
 from xotorch_amd.train.lora import apply_lora, lora_parameters
 from xotorch_amd.train.trainer import DPTrainer
@@ -19,14 +18,7 @@ model_id = sys.argv[1] if len(sys.argv) > 1 else "llama-3-8b"
 B, S = 8, 512
 cfg = config_from_hf(builtin_config(model_id), model_id)
 shard = Shard(model_id, 0, cfg.n_layers - 1, cfg.n_layers)
-prev = torch.get_default_dtype()
-torch.set_default_dtype(torch.bfloat16)
-with torch.device("meta"):
-  model = ShardedModel(cfg, shard)
-torch.set_default_dtype(prev)
-model = model.to_empty(device="cuda").to(torch.bfloat16)
-fast_random_init_gpu(model)
-model.reset_rope()
+model = build_shard_model(cfg, shard, torch.bfloat16, "cuda", fast_init=True)
 n_lora = apply_lora(model, rank=16)
 model.train()
 trainer = DPTrainer(model, lr=1e-4)

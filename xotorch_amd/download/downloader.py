@@ -22,7 +22,7 @@ from pathlib import Path
 from typing import Callable, Dict, List, Optional, Tuple
 
 from xotorch_amd.helpers import DEBUG, XOT_HOME, AsyncCallbackSystem
-from xotorch_amd.models.llama import hf_key_map
+from xotorch_amd.models.weights import hf_key_map
 from xotorch_amd.models.config import config_from_hf
 from xotorch_amd.models.registry import get_repo
 from xotorch_amd.shard import Shard

@@ -20,6 +20,8 @@ from typing import List, NamedTuple, Optional
 
 import torch
 
+from xotorch_amd import ops
+
 
 class LayerKV(NamedTuple):
   k: torch.Tensor
@@ -29,14 +31,9 @@ class LayerKV(NamedTuple):
   ksc: Optional[torch.Tensor] = None  # fp8 mode: per-row K scales [B, KVH, T32]
   vsc: Optional[torch.Tensor] = None  # fp8 mode: per-row V scales
 
-
-def _want_packed(device: str, head_dim: int, dtype: torch.dtype) -> bool:
-  return (
-    str(device).startswith("cuda")
-    and head_dim == 128
-    and dtype == torch.bfloat16
-    and os.getenv("XOT_MFMA_ATTN", "1") == "1"
-  )
+  def rows(self, b0: int, b1: int) -> "LayerKV":
+    """Views of batch rows [b0, b1) over every field that is present."""
+    return LayerKV(*(t[b0:b1] if t is not None else None for t in self))
 
 
 class ShardKVCache:
@@ -52,43 +49,50 @@ class ShardKVCache:
     self.batch = batch
     self.caches: List[LayerKV] = []
     vd = v_dim if v_dim is not None else head_dim
-    packed = _want_packed(device, head_dim, dtype) and vd == head_dim
-    fp8_kv = packed and os.getenv("XOT_FP8_KV", "0") == "1"
-    # MLA latent cache (k = 512-dim latent, v = 64-dim roped shared key,
-    # one kv "head"): fragment-packed copies for the absorbed-MQA MFMA
-    # decode kernel (18 qk chunks / 32 pv groups — hip_ops.hip MLA section)
-    mla_packed = (
-      str(device).startswith("cuda") and dtype == torch.bfloat16
-      and n_kv_heads == 1 and head_dim == 512 and vd == 64
-      and os.getenv("XOT_MFMA_ATTN", "1") == "1"
-    )
     t32 = (capacity + 31) // 32 * 32
+    # fragment-packed second copies for the MFMA attention kernels: shapes of
+    # (kp, vp) and of the fp8 mode's per-row scale tensors, or none (plain)
+    packed = (str(device).startswith("cuda") and dtype == torch.bfloat16
+              and ops.mfma_attn_enabled())
+    if packed and head_dim == 128 and vd == 128:
+      # GQA: 16-position x 32-hd-chunk K tiles, 32-position x 16-hd-column V tiles
+      kp_shape = (batch, n_kv_heads, t32 // 16, 4, 64, 8)
+      vp_shape = (batch, n_kv_heads, 8, t32 // 32, 64, 8)
+      scale_shapes = [(batch, n_kv_heads, t32)] * 2
+    elif packed and n_kv_heads == 1 and head_dim == 512 and vd == 64:
+      # MLA latent cache (k = 512-dim latent, v = 64-dim roped shared key,
+      # one kv "head") for the absorbed-MQA decode kernel (18 qk chunks /
+      # 32 pv groups — hip_ops.hip MLA section); one scale tensor
+      kp_shape = (batch, t32 // 16, 18, 64, 8)
+      vp_shape = (batch, 32, t32 // 32, 64, 8)
+      scale_shapes = [(batch, t32)]
+    else:
+      kp_shape = vp_shape = None
+      scale_shapes = []
+    # fp8-KV: e4m3 packed copies (half the decode stream) + per-row scales;
+    # the plain cache stays in `dtype` for prefill
+    fp8_kv = kp_shape is not None and os.getenv("XOT_FP8_KV", "0") == "1"
     for _ in range(n_layers):
-      k = torch.zeros(batch, n_kv_heads, capacity, head_dim, dtype=dtype, device=device)
-      v = torch.zeros(batch, n_kv_heads, capacity, vd, dtype=dtype, device=device)
+      layer = [torch.zeros(batch, n_kv_heads, capacity, head_dim, dtype=dtype, device=device),
+               torch.zeros(batch, n_kv_heads, capacity, vd, dtype=dtype, device=device)]
+      if kp_shape is not None:
+        pdt = torch.uint8 if fp8_kv else dtype
+        layer += [torch.zeros(kp_shape, dtype=pdt, device=device),
+                  torch.zeros(vp_shape, dtype=pdt, device=device)]
       if fp8_kv:
-        # e4m3 packed copies (half the decode stream) + per-row scales;
-        # plain bf16 cache stays for prefill
-        kp = torch.zeros(batch, n_kv_heads, t32 // 16, 4, 64, 8, dtype=torch.uint8, device=device)
-        vp = torch.zeros(batch, n_kv_heads, 8, t32 // 32, 64, 8, dtype=torch.uint8, device=device)
-        ksc = torch.ones(batch, n_kv_heads, t32, dtype=torch.float32, device=device)
-        vsc = torch.ones(batch, n_kv_heads, t32, dtype=torch.float32, device=device)
-        self.caches.append(LayerKV(k, v, kp, vp, ksc, vsc))
-      elif packed:
-        kp = torch.zeros(batch, n_kv_heads, t32 // 16, 4, 64, 8, dtype=dtype, device=device)
-        vp = torch.zeros(batch, n_kv_heads, 8, t32 // 32, 64, 8, dtype=dtype, device=device)
-        self.caches.append(LayerKV(k, v, kp, vp))
-      elif mla_packed and os.getenv("XOT_FP8_KV", "0") == "1":
-        kp = torch.zeros(batch, t32 // 16, 18, 64, 8, dtype=torch.uint8, device=device)
-        vp = torch.zeros(batch, 32, t32 // 32, 64, 8, dtype=torch.uint8, device=device)
-        ksc = torch.ones(batch, t32, dtype=torch.float32, device=device)
-        self.caches.append(LayerKV(k, v, kp, vp, ksc))
-      elif mla_packed:
-        kp = torch.zeros(batch, t32 // 16, 18, 64, 8, dtype=dtype, device=device)
-        vp = torch.zeros(batch, 32, t32 // 32, 64, 8, dtype=dtype, device=device)
-        self.caches.append(LayerKV(k, v, kp, vp))
-      else:
-        self.caches.append(LayerKV(k, v))
+        layer += [torch.ones(s, dtype=torch.float32, device=device) for s in scale_shapes]
+      self.caches.append(LayerKV(*layer))
+
+  @classmethod
+  def for_config(cls, cfg, n_layers: int, batch: int, capacity: int,
+                 dtype: torch.dtype = torch.bfloat16, device: str = "cpu") -> "ShardKVCache":
+    """The cache `cfg`'s decoder expects (ModelConfig.kv_cache_dims())."""
+    heads, k_dim, v_dim = cfg.kv_cache_dims()
+    return cls(n_layers, batch, heads, capacity, k_dim, dtype, device, v_dim=v_dim)
+
+  def rows(self, b0: int, b1: int) -> List[LayerKV]:
+    """Every layer's LayerKV.rows(b0, b1): a batch slice of the whole cache."""
+    return [c.rows(b0, b1) for c in self.caches]
 
   def __getitem__(self, i):
     return self.caches[i]

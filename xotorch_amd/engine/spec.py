@@ -27,7 +27,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from xotorch_amd.engine.kvcache import ShardKVCache
-from xotorch_amd.models import model_class_for
+from xotorch_amd.models.build import build_shard_model
 from xotorch_amd.models.config import ModelConfig, config_from_hf
 from xotorch_amd.models.registry import builtin_config
 from xotorch_amd.shard import Shard
@@ -56,35 +56,18 @@ class SpeculativeDecoder:
     self.device, self.dtype = device, dtype
     self.gamma = gamma
     self.max_seq = min(max_seq, target_cfg.max_seq_len, draft_cfg.max_seq_len)
-    th, tk, tv = target_cfg.kv_cache_dims()
-    dh, dk, dv = draft_cfg.kv_cache_dims()
-    self.t_cache = ShardKVCache(target_cfg.n_layers, 1, th, self.max_seq, tk, dtype, device, v_dim=tv)
-    self.d_cache = ShardKVCache(draft_cfg.n_layers, 1, dh, self.max_seq, dk, dtype, device, v_dim=dv)
+    self.t_cache = ShardKVCache.for_config(target_cfg, target_cfg.n_layers, 1, self.max_seq, dtype, device)
+    self.d_cache = ShardKVCache.for_config(draft_cfg, draft_cfg.n_layers, 1, self.max_seq, dtype, device)
 
   @classmethod
   def from_model_ids(cls, target_id: str, draft_id: str, device="cuda",
                      dtype=torch.bfloat16, gamma: int = 4, seed: int = 1234, **kw):
-    from xotorch_amd.models.weights import fast_random_init_gpu, random_init
     models = []
     cfgs = []
     for mid in (target_id, draft_id):
       cfg = config_from_hf(builtin_config(mid), mid)
       shard = Shard(mid, 0, cfg.n_layers - 1, cfg.n_layers)
-      cls_ = model_class_for(cfg)
-      prev = torch.get_default_dtype()
-      torch.set_default_dtype(dtype)
-      try:
-        with torch.device("meta"):
-          m = cls_(cfg, shard)
-      finally:
-        torch.set_default_dtype(prev)
-      m = m.to_empty(device=device).to(dtype)
-      if device == "cuda" and cfg.dim >= 2048:
-        fast_random_init_gpu(m, seed)
-      else:
-        random_init(m, seed)
-      m.reset_rope()
-      m.eval()
+      m = build_shard_model(cfg, shard, dtype, device, seed=seed, fast_init=True)
       if device == "cuda":
         m.pack_decode_weights(reserve_bytes=8 << 30)
       models.append(m)

@@ -29,10 +29,9 @@ from xotorch_amd.engine.interface import InferenceEngine
 from xotorch_amd.engine.kvcache import ShardKVCache
 from xotorch_amd.engine.state import ShardInferenceState
 from xotorch_amd.engine.tokenizers import DummyTokenizer, resolve_tokenizer
+from xotorch_amd.models.build import build_shard_model
 from xotorch_amd.models.config import ModelConfig, config_from_hf
-from xotorch_amd.models.llama import ShardedModel
 from xotorch_amd.models.registry import builtin_config, get_repo
-from xotorch_amd.models.weights import load_shard_weights, random_init
 from xotorch_amd.shard import Shard
 
 TEMP = float(os.getenv("XOT_TEMP", "0.6"))
@@ -61,7 +60,7 @@ class TorchEngine(InferenceEngine):
     self.device = device
     self.dtype = dtype if dtype is not None else (torch.bfloat16 if device == "cuda" else torch.float32)
     self.shard: Optional[Shard] = None
-    self.model: Optional[ShardedModel] = None
+    self.model: Optional[torch.nn.Module] = None
     self.cfg: Optional[ModelConfig] = None
     self.tokenizer = None
     self.sessions: Dict[str, Session] = {}
@@ -104,36 +103,11 @@ class TorchEngine(InferenceEngine):
     if cfg_dict is None:
       raise ValueError(f"no config available for model {shard.model_id}")
     cfg = config_from_hf(cfg_dict, model_id=shard.model_id)
-    if cfg.model_type == "gemma2":
-      from xotorch_amd.models.gemma2 import Gemma2Model
-      model_cls = Gemma2Model
-    elif cfg.model_type in ("deepseek_v3", "deepseek_v2"):
-      from xotorch_amd.models.deepseek_v3 import DeepseekV3Model
-      model_cls = DeepseekV3Model
-    else:
-      model_cls = ShardedModel
-    # construct at the target dtype so to_empty materializes it directly
-    # (fp32-then-cast would peak at 2x the weight bytes)
-    prev_dtype = torch.get_default_dtype()
-    torch.set_default_dtype(self.dtype)
-    try:
-      with torch.device("meta"):
-        model = model_cls(cfg, shard)
-    finally:
-      torch.set_default_dtype(prev_dtype)
-    model = model.to_empty(device=self.device)
-    model = model.to(self.dtype)
-    # recompute rope tables (to_empty leaves buffers uninitialized); each
-    # decoder derives its own table shape (MLA uses qk_rope_head_dim)
-    model.reset_rope()
-    if model_dir is not None and (
+    has_weights = model_dir is not None and (
       (Path(model_dir) / "model.safetensors.index.json").exists() or (Path(model_dir) / "model.safetensors").exists()
-    ):
-      load_shard_weights(model, Path(model_dir), device="cpu")
-      model = model.to(self.device)
-    else:
-      random_init(model)
-    model.eval()
+    )
+    model = build_shard_model(cfg, shard, self.dtype, self.device,
+                              model_dir=model_dir if has_weights else None)
     if self.device == "cuda":
       # decode-GEMM weight prepack (auto-picked vs hipBLASLt per shape at
       # first decode); keep headroom for per-request KV caches
@@ -147,11 +121,8 @@ class TorchEngine(InferenceEngine):
   def _session(self, request_id: str, batch: int, total_len: int) -> Session:
     sess = self.sessions.get(request_id)
     if sess is None or sess.cache.batch != batch or sess.cache.capacity < total_len:
-      heads, k_dim, v_dim = self.cfg.kv_cache_dims()
-      cache = ShardKVCache(
-        n_layers=self.shard.get_layer_count(), batch=batch, n_kv_heads=heads,
-        capacity=total_len, head_dim=k_dim, dtype=self.dtype, device=self.device, v_dim=v_dim,
-      )
+      cache = ShardKVCache.for_config(self.cfg, self.shard.get_layer_count(), batch, total_len,
+                                      self.dtype, self.device)
       sess = Session(cache=cache, state=ShardInferenceState(total_len=total_len, batch=batch))
       self.sessions[request_id] = sess
     return sess

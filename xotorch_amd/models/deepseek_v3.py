@@ -24,16 +24,15 @@ latent [B, 1, T, kv_lora_rank] and v tensor stores the roped shared key
 """
 from __future__ import annotations
 
-from typing import List
-
 import torch
 import torch.nn as nn
 
 from xotorch_amd import ops
+from xotorch_amd.models.base import ShardBase, ragged_decode_rows
 from xotorch_amd.models.config import ModelConfig
 from xotorch_amd.models.llama import XotLinear
 from xotorch_amd.models.moe import expert_loop, moe_decode, sorted_expert_prefill
-from xotorch_amd.ops.torch_ref import rope_cos_sin
+from xotorch_amd.ops.torch_ref import rmsnorm as rmsnorm_ref
 from xotorch_amd.shard import Shard
 
 
@@ -41,9 +40,7 @@ def _rms(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
   if x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 \
      and x.shape[-1] % 8 == 0 and x.shape[-1] <= 16384:
     return ops.rmsnorm(x.contiguous(), w, eps)  # one HIP launch vs ~4 torch ops
-  xf = x.float()
-  out = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
-  return (w.float() * out).to(x.dtype)
+  return rmsnorm_ref(x, w, eps)
 
 
 def _rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, interleave: bool) -> torch.Tensor:
@@ -62,6 +59,17 @@ def _rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, interleave: boo
     half = x.shape[-1] // 2
     x1, x2 = xf[..., :half], xf[..., half:]
   return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).to(x.dtype)
+
+
+def _rope_rows(cos, sin, positions, B: int, S: int):
+  """The rope tables' rows at `positions` ([S] shared, or B*S per-row), in
+  the shape _rope takes."""
+  pidx = positions.reshape(-1).long()
+  cs, sn = cos[pidx], sin[pidx]
+  if pidx.numel() == B * S and pidx.numel() != S:
+    cs = cs.view(B, S, -1)
+    sn = sn.view(B, S, -1)
+  return cs, sn
 
 
 class MLAttention(nn.Module):
@@ -103,61 +111,42 @@ class MLAttention(nn.Module):
 
     ckv = self.kv_a_proj_with_mqa(x)
 
-    kp = kv[2] if len(kv) > 2 else None
-    hip = None
-    if kp is not None and x.is_cuda and x.dtype == torch.bfloat16:
-      from xotorch_amd.ops import _load_hip
-      hip = _load_hip()
+    # latent cache: k tensor <- kv_nope [B,1,T,kv_lora], v tensor <- roped
+    # shared key [B,1,T,rope_d]
+    lat_c, rot_c = kv.k, kv.v
     decode = is_decode or (S == 1 and (start_pos > 0 or start_pos < 0))
-    if hip is not None:
+    if kv.kp is not None and x.is_cuda and x.dtype == torch.bfloat16 and ops.hip_available():
       # fused KV-side prep: latent RMSNorm + shared-key rope + plain AND
       # fragment-packed cache writes in ONE launch (device positions —
       # graph-capturable; replaces ~10 torch launches per layer)
-      hip.mla_prep_append(ckv.contiguous(), self.kv_a_layernorm, cos, sin,
-                          positions.to(torch.int32).contiguous(), kv[0], kv[1],
-                          kp, kv[3], cfg.norm_eps, cfg.rope_interleave,
-                          kv[4] if len(kv) > 4 else None)
+      ops.mla_prep_append(ckv.contiguous(), self.kv_a_layernorm, cos, sin,
+                          positions.to(torch.int32).contiguous(), lat_c, rot_c,
+                          kv.kp, kv.vp, cfg.norm_eps, cfg.rope_interleave, kv.ksc)
       if decode and not torch.is_grad_enabled():
         if seq_lens is None:
           seq_lens = torch.full((B,), start_pos + 1, dtype=torch.int32, device=x.device)
-        return self._decode_mfma(x, q, q_pass, kv, seq_lens, hip, positions, cos, sin)
+        return self._decode_mfma(x, q, q_pass, kv, seq_lens, positions, cos, sin)
       if start_pos < 0:
         start_pos = int(positions.reshape(-1)[0])
+      q_rot = _rope(q_rot, *_rope_rows(cos, sin, positions, B, S), cfg.rope_interleave)
       if not torch.is_grad_enabled():
         # GPU prefill: query-chunked bf16 attention (the eager path below
         # materializes [B,H,S,T] fp32 scores — 67 GB transient per layer
         # at B=64, S=512)
-        q_rot = self._rope_q(q_rot, cos, sin, positions, B, S)
         return self._prefill_absorbed(x, q_pass, q_rot, kv, start_pos, S)
-      q_rot = self._rope_q(q_rot, cos, sin, positions, B, S)
     else:
-      q_rot = self._rope_q(q_rot, cos, sin, positions, B, S)
-      pidx = positions.reshape(-1).long()
-      cs, sn = cos[pidx], sin[pidx]
-      if pidx.numel() == B * S and pidx.numel() != S:
-        cs = cs.view(B, S, -1)
-        sn = sn.view(B, S, -1)
+      cs, sn = _rope_rows(cos, sin, positions, B, S)
+      q_rot = _rope(q_rot, cs, sn, cfg.rope_interleave)
       kv_nope, k_rot = ckv[..., : cfg.kv_lora_rank], ckv[..., cfg.kv_lora_rank:]
       kv_nope = _rms(kv_nope, self.kv_a_layernorm, cfg.norm_eps)
       k_rot = _rope(k_rot.view(B, S, 1, rope_d), cs, sn, cfg.rope_interleave)
       if start_pos < 0:  # ring/serve decode contract: derive from positions
-        prow = positions.reshape(-1)
-        if prow.numel() == B * S and S == 1 and B > 1 and int(prow.min()) != int(prow.max()):
-          # ragged per-row positions on the EAGER path (continuous-batching
-          # slots on CPU / no packed cache): correctness-first row loop
-          outs = []
-          for b in range(B):
-            outs.append(self.forward(x[b:b + 1], cos, sin, prow[b:b + 1],
-                                     tuple(t[b:b + 1] if t is not None else None for t in kv),
-                                     int(prow[b]), is_decode, None))
-          return torch.cat(outs, dim=0)
-        start_pos = int(prow[0])
-      # latent cache: k tensor <- kv_nope [B,1,T,kv_lora], v tensor <- roped
-      # shared key [B,1,T,rope_d]
-      lat_c, rot_c = kv[0], kv[1]
+        out = ragged_decode_rows(self, x, cos, sin, positions, kv, is_decode)
+        if out is not None:
+          return out
+        start_pos = int(positions.reshape(-1)[0])
       lat_c[:, 0, start_pos: start_pos + S] = kv_nope
       rot_c[:, 0, start_pos: start_pos + S] = k_rot[:, :, 0, :]
-    lat_c, rot_c = kv[0], kv[1]
     total = start_pos + S
     lat = lat_c[:, 0, :total]                                   # [B, T, kv_lora]
     krot = rot_c[:, 0, :total]                                  # [B, T, rope_d]
@@ -177,14 +166,6 @@ class MLAttention(nn.Module):
     return self.o_proj(out.reshape(B, S, H * vd))
 
 
-  def _rope_q(self, q_rot, cos, sin, positions, B, S):
-    pidx = positions.reshape(-1).long()
-    cs, sn = cos[pidx], sin[pidx]
-    if pidx.numel() == B * S and pidx.numel() != S:
-      cs = cs.view(B, S, -1)
-      sn = sn.view(B, S, -1)
-    return _rope(q_rot, cs, sn, self.cfg.rope_interleave)
-
   def _prefill_absorbed(self, x, q_pass, q_rot, kv, start_pos: int, S: int):
     """GPU prefill: expand the latent cache through kv_b into per-head
     K/V (qk dim 192 -> flash-eligible) and run sdpa causal; when the
@@ -197,8 +178,8 @@ class MLAttention(nn.Module):
     B, H = x.shape[0], cfg.n_heads
     nope, vd = cfg.qk_nope_head_dim, cfg.v_head_dim
     total = start_pos + S
-    lat = kv[0][:, 0, :total]                                   # [B,T,512]
-    rot = kv[1][:, 0, :total]                                   # [B,T,64]
+    lat = kv.k[:, 0, :total]                                    # [B,T,512]
+    rot = kv.v[:, 0, :total]                                    # [B,T,64]
     kvx = self.kv_b_proj(lat).view(B, total, H, nope + vd)
     k = torch.cat([kvx[..., :nope],
                    rot[:, :, None, :].expand(B, total, H, -1)], dim=-1)
@@ -218,7 +199,7 @@ class MLAttention(nn.Module):
     out = out.permute(0, 2, 1, 3).reshape(B, S, H * vd)
     return self.o_proj(out)
 
-  def _decode_mfma(self, x, q_raw, q_pass, kv, seq_lens, hip, positions, cos, sin):
+  def _decode_mfma(self, x, q_raw, q_pass, kv, seq_lens, positions, cos, sin):
     """Absorbed-latent MFMA decode: kv_b is folded into q and out, so
     attention runs as MQA over the packed 1152 B/token latent stream
     (hip_ops.hip attn_decode_mla); the q tail rope + assembly is one
@@ -231,15 +212,12 @@ class MLAttention(nn.Module):
       self._w_k = W[:, :nope, :].contiguous()   # [H, nope, lat]
       self._w_v = W[:, nope:, :].contiguous()   # [H, vd, lat]
     q_lat = torch.einsum("bshn,hnl->bshl", q_pass.to(x.dtype), self._w_k)
-    fp8 = kv[2].dtype == torch.uint8
-    prep = hip.mla_q_prep(q_raw.contiguous(), q_lat.contiguous(), cos, sin,
+    fp8 = kv.kp.dtype == torch.uint8
+    prep = ops.mla_q_prep(q_raw.contiguous(), q_lat.contiguous(), cos, sin,
                           positions.to(torch.int32).contiguous(),
                           nope, cfg.rope_interleave, fp8)
-    if fp8:
-      out_lat = hip.attn_decode_mla(prep[0], kv[2], kv[3], seq_lens, self.scale,
-                                    prep[1], kv[4])
-    else:
-      out_lat = hip.attn_decode_mla(prep[0], kv[2], kv[3], seq_lens, self.scale)
+    out_lat = ops.attn_decode_mla(prep[0], kv.kp, kv.vp, seq_lens, self.scale,
+                                  prep[1] if fp8 else None, kv.ksc if fp8 else None)
     out = torch.einsum("bhl,hdl->bhd", out_lat, self._w_v).to(x.dtype)
     return self.o_proj(out.reshape(B, 1, H * vd))
 
@@ -352,35 +330,19 @@ class DsLayer(nn.Module):
     return h + self.mlp(_rms(h, self.post_attention_layernorm, self.eps))
 
 
-class DeepseekV3Model(nn.Module):
+class DeepseekV3Model(ShardBase):
   """Layer range [shard.start_layer .. shard.end_layer]; engine-contract
   forward (same as ShardedModel / Gemma2Model)."""
 
   def __init__(self, cfg: ModelConfig, shard: Shard):
-    super().__init__()
-    self.cfg = cfg
-    self.shard = shard
-    if shard.is_first_layer:
-      self.embed_tokens = nn.Embedding(cfg.vocab_size, cfg.dim)
+    # per-pair rope tables at the ROPE head dim
+    super().__init__(cfg, shard, rope_dim=cfg.qk_rope_head_dim)
     self.layers = nn.ModuleDict(
       {str(i): DsLayer(cfg, i) for i in range(shard.start_layer, shard.end_layer + 1)}
     )
     if shard.is_last_layer:
       self.norm = nn.Parameter(torch.ones(cfg.dim))
       self.lm_head = nn.Linear(cfg.dim, cfg.vocab_size, bias=False)
-    # per-pair rope tables at the ROPE head dim
-    cos, sin = rope_cos_sin(cfg.qk_rope_head_dim, cfg.max_seq_len, cfg.rope_theta, cfg.rope_scaling)
-    self.register_buffer("rope_cos", cos, persistent=False)
-    self.register_buffer("rope_sin", sin, persistent=False)
-
-  def reset_rope(self):
-    cos, sin = rope_cos_sin(self.cfg.qk_rope_head_dim, self.cfg.max_seq_len, self.cfg.rope_theta,
-                            self.cfg.rope_scaling, device=self.rope_cos.device)
-    self.rope_cos, self.rope_sin = cos, sin
-
-  @property
-  def local_layer_ids(self) -> List[int]:
-    return list(range(self.shard.start_layer, self.shard.end_layer + 1))
 
   def pack_decode_weights(self, reserve_bytes: int = 0) -> int:
     """MLA projections + dense/shared MLPs get the packed skinny-GEMM
@@ -410,20 +372,15 @@ class DeepseekV3Model(nn.Module):
     if caches is None:
       raise NotImplementedError("MLA training forward is not implemented (inference only)")
     h = self.embed_tokens(x) if x.dtype in (torch.int32, torch.int64) else x
-    if positions.dim() == 0:
-      positions = positions.reshape(1)
+    caches, positions, use_ckpt = self._enter(caches, positions)  # use_ckpt: never, caches are given
     for idx, lid in enumerate(self.local_layer_ids):
-      h = self.layers[str(lid)](h, self.rope_cos, self.rope_sin, positions, caches[idx],
-                                start_pos, is_decode, seq_lens)
+      h = self._run_layer(self.layers[str(lid)], use_ckpt, h, positions, caches[idx],
+                          start_pos, is_decode, seq_lens)
     if not self.shard.is_last_layer:
       return h
-    if last_only and h.shape[1] > 1:
-      h = h[:, -1:, :]
-    logits = torch.nn.functional.linear(_rms(h, self.norm, cfg.norm_eps),
-                                        self.head_weight().to(h.dtype))
-    if is_decode or last_only:
-      return logits[:, -1, :]
-    return logits
+    h = _rms(self._last_rows(h, last_only), self.norm, cfg.norm_eps)
+    logits = torch.nn.functional.linear(h, self.head_weight().to(h.dtype))
+    return self._pick(logits, is_decode, last_only)
 
 
 def hf_key_map_deepseek(shard: Shard, cfg: ModelConfig):

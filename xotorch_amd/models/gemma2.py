@@ -24,17 +24,13 @@ last owns the final norm + tied head; caches are the engine's LayerKV pairs.
 """
 from __future__ import annotations
 
-import math
-import os
-from typing import List, Optional
-
 import torch
 import torch.nn as nn
 
 from xotorch_amd import ops
+from xotorch_amd.models.base import ShardBase, ragged_decode_rows
 from xotorch_amd.models.config import ModelConfig
 from xotorch_amd.models.llama import XotLinear, pack_decode_weights
-from xotorch_amd.ops.torch_ref import rope_cos_sin
 from xotorch_amd.shard import Shard
 
 
@@ -51,7 +47,7 @@ def _softcap(x: torch.Tensor, cap: float) -> torch.Tensor:
 def _use_mfma(x: torch.Tensor, hd: int, kv) -> bool:
   return (
     x.is_cuda and x.dtype == torch.bfloat16 and hd == 128
-    and len(kv) > 2 and kv[2] is not None and ops.hip_available()
+    and kv.kp is not None and ops.hip_available()
   )
 
 
@@ -77,35 +73,26 @@ class Gemma2Attention(nn.Module):
     qkv = self.qkv_proj(x)  # [B, S, (H+2KVH)*hd]
     if kv is None:
       return self._forward_nocache(qkv, cos, sin, positions, cap)
-    k_cache, v_cache = kv[0], kv[1]
+    k_cache, v_cache = kv.k, kv.v
     if _use_mfma(qkv, hd, kv):
-      kp, vp = kv[2], kv[3]
-      ksc = kv[4] if len(kv) > 4 else None
-      vsc = kv[5] if len(kv) > 5 else None
-      ops.rope_qkv_append(qkv, cos, sin, positions, k_cache, v_cache, H, KVH, hd, kp, vp,
-                          k_scale=ksc, v_scale=vsc)
+      ops.rope_qkv_append(qkv, cos, sin, positions, k_cache, v_cache, H, KVH, hd, kv.kp, kv.vp,
+                          k_scale=kv.ksc, v_scale=kv.vsc)
       q = qkv[:, :, : H * hd].view(B, S, H, hd)
       if is_decode:
         sl = seq_lens if seq_lens is not None else start_pos + 1
-        out = ops.attn_decode(q, k_cache, v_cache, sl, kp, vp,
+        out = ops.attn_decode(q, k_cache, v_cache, sl, kv.kp, kv.vp,
                               scale=self.scale, softcap=cap, window=self.window,
-                              k_scale=ksc, v_scale=vsc)
+                              k_scale=kv.ksc, v_scale=kv.vsc)
       else:
-        out = ops.attn_prefill(q, k_cache, v_cache, start_pos, S, kp, vp,
+        out = ops.attn_prefill(q, k_cache, v_cache, start_pos, S, kv.kp, kv.vp,
                                scale=self.scale, softcap=cap, window=self.window)
       return self.o_proj(out.reshape(B, S, H * hd))
     # eager oracle path (CPU / hd != 128): split the fused projection
     if start_pos < 0:  # ring/serve decode contract: derive from positions
-      prow = positions.reshape(-1)
-      if prow.numel() == B * S and S == 1 and B > 1 and int(prow.min()) != int(prow.max()):
-        # ragged per-row slot positions: correctness-first row loop
-        outs = []
-        for b in range(B):
-          outs.append(self.forward(x[b:b + 1], cos, sin, prow[b:b + 1],
-                                   tuple(t[b:b + 1] if t is not None else None for t in kv),
-                                   int(prow[b]), is_decode, None))
-        return torch.cat(outs, dim=0)
-      start_pos = int(prow[0])
+      out = ragged_decode_rows(self, x, cos, sin, positions, kv, is_decode)
+      if out is not None:
+        return out
+      start_pos = int(positions.reshape(-1)[0])
     from xotorch_amd.ops import torch_ref as tr
     q, k, v = torch.split(qkv, [H * hd, KVH * hd, KVH * hd], dim=-1)
     q = q.view(B, S, H, hd)
@@ -199,16 +186,12 @@ class Gemma2Layer(nn.Module):
     return res + _rms(hs, self.post_feedforward_layernorm, self.eps)
 
 
-class Gemma2Model(nn.Module):
+class Gemma2Model(ShardBase):
   """Layer range [shard.start_layer .. shard.end_layer] of a Gemma2 model.
   Same forward contract as ShardedModel (engine-compatible)."""
 
   def __init__(self, cfg: ModelConfig, shard: Shard):
-    super().__init__()
-    self.cfg = cfg
-    self.shard = shard
-    if shard.is_first_layer:
-      self.embed_tokens = nn.Embedding(cfg.vocab_size, cfg.dim)
+    super().__init__(cfg, shard, rope_dim=cfg.head_dim)
     self.layers = nn.ModuleDict(
       {str(i): Gemma2Layer(cfg, i) for i in range(shard.start_layer, shard.end_layer + 1)}
     )
@@ -217,18 +200,6 @@ class Gemma2Model(nn.Module):
       if not shard.is_first_layer:
         # tied embeddings, but the owner shard is elsewhere: local head copy
         self.lm_head = nn.Linear(cfg.dim, cfg.vocab_size, bias=False)
-    cos, sin = rope_cos_sin(cfg.head_dim, cfg.max_seq_len, cfg.rope_theta, cfg.rope_scaling)
-    self.register_buffer("rope_cos", cos, persistent=False)
-    self.register_buffer("rope_sin", sin, persistent=False)
-
-  def reset_rope(self):
-    cos, sin = rope_cos_sin(self.cfg.head_dim, self.cfg.max_seq_len, self.cfg.rope_theta,
-                            self.cfg.rope_scaling, device=self.rope_cos.device)
-    self.rope_cos, self.rope_sin = cos, sin
-
-  @property
-  def local_layer_ids(self) -> List[int]:
-    return list(range(self.shard.start_layer, self.shard.end_layer + 1))
 
   def pack_decode_weights(self, reserve_bytes: int = 8 << 30) -> int:
     return pack_decode_weights(self, reserve_bytes)  # the policy ShardedModel uses
@@ -245,29 +216,17 @@ class Gemma2Model(nn.Module):
       h = self.embed_tokens(x) * torch.tensor(cfg.dim ** 0.5, dtype=self.embed_tokens.weight.dtype)
     else:
       h = x
-    if positions.dim() == 0:
-      positions = positions.reshape(1)
-    use_ckpt = (caches is None and self.training and torch.is_grad_enabled()
-                and os.getenv("XOT_ACT_CKPT", "0") == "1")
+    caches, positions, use_ckpt = self._enter(caches, positions)
     for idx, lid in enumerate(self.local_layer_ids):
       kv = caches[idx] if caches is not None else None
-      if use_ckpt:
-        h = torch.utils.checkpoint.checkpoint(
-          self.layers[str(lid)], h, self.rope_cos, self.rope_sin, positions, kv,
-          start_pos, is_decode, seq_lens, use_reentrant=False)
-      else:
-        h = self.layers[str(lid)](h, self.rope_cos, self.rope_sin, positions, kv,
-                                  start_pos, is_decode, seq_lens)
+      h = self._run_layer(self.layers[str(lid)], use_ckpt, h, positions, kv,
+                          start_pos, is_decode, seq_lens)
     if not self.shard.is_last_layer:
       return h
-    if last_only and h.shape[1] > 1:
-      h = h[:, -1:, :]
-    h = _rms(h, self.norm, cfg.norm_eps)
+    h = _rms(self._last_rows(h, last_only), self.norm, cfg.norm_eps)
     logits = torch.nn.functional.linear(h, self.head_weight().to(h.dtype))
     logits = _softcap(logits.float(), cfg.final_logit_softcapping).to(logits.dtype)
-    if is_decode or last_only:
-      return logits[:, -1, :]
-    return logits
+    return self._pick(logits, is_decode, last_only)
 
 
 def hf_key_map_gemma2(shard: Shard, cfg: ModelConfig):

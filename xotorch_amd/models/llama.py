@@ -15,18 +15,18 @@ and llm_utils.py:335-489), built for MI355X execution:
 """
 from __future__ import annotations
 
-import math
 import os
-from typing import List, Optional, Tuple
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
 from xotorch_amd import ops
+from xotorch_amd.engine.kvcache import LayerKV
+from xotorch_amd.models.base import ShardBase
 from xotorch_amd.models.config import ModelConfig
 from xotorch_amd.models.linear import XotLinear, auto_pick, decode_rows
 from xotorch_amd.models.moe import expert_loop, moe_decode, sorted_expert_prefill
-from xotorch_amd.ops.torch_ref import rope_cos_sin
 from xotorch_amd.shard import Shard
 
 
@@ -89,22 +89,17 @@ class Attention(nn.Module):
     B, S, _ = x.shape
     cfg = self.cfg
     H, hd = cfg.n_heads, cfg.head_dim
-    k_cache, v_cache = kv[0], kv[1]
-    kp = kv[2] if len(kv) > 2 else None  # MFMA-packed cache copies (GPU, hd=128)
-    vp = kv[3] if len(kv) > 3 else None
-    ksc = kv[4] if len(kv) > 4 else None  # fp8-KV mode scales
-    vsc = kv[5] if len(kv) > 5 else None
     qkv = self.qkv_proj(x)  # [B, S, (H+2KVH)*hd]
     qn = self.q_norm if cfg.qk_norm else None
     kn = self.k_norm if cfg.qk_norm else None
-    ops.rope_qkv_append(qkv, cos, sin, positions, k_cache, v_cache, H, cfg.n_kv_heads, hd, kp, vp,
-                        qn, kn, cfg.norm_eps, ksc, vsc)
+    ops.rope_qkv_append(qkv, cos, sin, positions, kv.k, kv.v, H, cfg.n_kv_heads, hd, kv.kp, kv.vp,
+                        qn, kn, cfg.norm_eps, kv.ksc, kv.vsc)
     q = qkv[:, :, : H * hd].view(B, S, H, hd)  # strided view; kernels accept it
     if is_decode:
       sl = seq_lens if seq_lens is not None else start_pos + 1
-      out = ops.attn_decode(q, k_cache, v_cache, sl, kp, vp, k_scale=ksc, v_scale=vsc)
+      out = ops.attn_decode(q, kv.k, kv.v, sl, kv.kp, kv.vp, k_scale=kv.ksc, v_scale=kv.vsc)
     else:
-      out = ops.attn_prefill(q, k_cache, v_cache, start_pos, S, kp, vp)
+      out = ops.attn_prefill(q, kv.k, kv.v, start_pos, S, kv.kp, kv.vp)
     return self.o_proj(out.reshape(B, S, H * hd))
 
 
@@ -314,15 +309,11 @@ def pack_decode_weights(model, reserve_bytes: int) -> int:
   return packed
 
 
-class ShardedModel(nn.Module):
+class ShardedModel(ShardBase):
   """The layer range [shard.start_layer .. shard.end_layer] of one model."""
 
   def __init__(self, cfg: ModelConfig, shard: Shard):
-    super().__init__()
-    self.cfg = cfg
-    self.shard = shard
-    if shard.is_first_layer:
-      self.embed_tokens = nn.Embedding(cfg.vocab_size, cfg.dim)
+    super().__init__(cfg, shard, rope_dim=cfg.head_dim)
     self.layers = nn.ModuleDict({str(i): DecoderLayer(cfg) for i in range(shard.start_layer, shard.end_layer + 1)})
     if shard.is_last_layer:
       self.norm = RMSNorm(cfg.dim, cfg.norm_eps)
@@ -332,29 +323,6 @@ class ShardedModel(nn.Module):
         # tied embeddings but the first shard (owner of embed_tokens) is
         # elsewhere: keep a local copy of the embedding matrix as the head.
         self.lm_head = XotLinear(cfg.dim, cfg.vocab_size, bias=False)
-    cos, sin = rope_cos_sin(cfg.head_dim, cfg.max_seq_len, cfg.rope_theta, cfg.rope_scaling)
-    self.register_buffer("rope_cos", cos, persistent=False)
-    self.register_buffer("rope_sin", sin, persistent=False)
-
-  def reset_rope(self):
-    """(Re)compute the fp32 RoPE tables on the current device. Required after
-    meta-device construction + to_empty (tables are uninitialized memory)."""
-    cos, sin = rope_cos_sin(self.cfg.head_dim, self.cfg.max_seq_len, self.cfg.rope_theta,
-                            self.cfg.rope_scaling, device=self.rope_cos.device)
-    self.rope_cos = cos
-    self.rope_sin = sin
-
-  def _apply(self, fn, recurse=True):
-    # keep RoPE tables fp32 (HIP kernel contract): a model-wide .to(bf16)
-    # would quantize them; recompute at full precision on the new device.
-    super()._apply(fn, recurse)
-    if self.rope_cos.device.type != "meta" and self.rope_cos.dtype != torch.float32:
-      self.reset_rope()
-    return self
-
-  @property
-  def local_layer_ids(self) -> List[int]:
-    return list(range(self.shard.start_layer, self.shard.end_layer + 1))
 
   def pack_decode_weights(self, reserve_bytes: int = 8 << 30) -> int:
     return pack_decode_weights(self, reserve_bytes)
@@ -367,7 +335,7 @@ class ShardedModel(nn.Module):
   def forward(
     self,
     x: torch.Tensor,
-    caches: List[Tuple[torch.Tensor, torch.Tensor]],
+    caches: Optional[List[LayerKV]],
     positions: torch.Tensor,
     start_pos: int,
     is_decode: bool = False,
@@ -378,7 +346,7 @@ class ShardedModel(nn.Module):
     """Run this shard.
 
     x: [B,S] int tokens (first shard) or [B,S,D] hidden states.
-    caches: one (k_cache, v_cache) pair per LOCAL layer.
+    caches: one LayerKV (or plain tuple of its fields) per LOCAL layer.
     positions: absolute position ids [S] or [B,S] (device tensor).
     carry_norm: every layer computes the norm that follows it in its down
     projection's epilogue (DecoderLayer.forward_carry). None = on for GPU
@@ -392,12 +360,7 @@ class ShardedModel(nn.Module):
       h = self.embed_tokens(x)
     else:
       h = x
-    cos, sin = self.rope_cos, self.rope_sin
-    # caches=None selects the cache-free training forward; activation
-    # checkpointing (on by default when training under grad) trades the
-    # per-layer activation residency for a recompute in backward
-    use_ckpt = (caches is None and self.training and torch.is_grad_enabled()
-                and os.getenv("XOT_ACT_CKPT", "0") == "1")
+    caches, positions, use_ckpt = self._enter(caches, positions)
     if carry_norm is None:
       carry_norm = (h.is_cuda and h.dtype == torch.bfloat16 and not torch.is_grad_enabled()
                     and ops.fuse_epilogue_enabled())
@@ -416,27 +379,19 @@ class ShardedModel(nn.Module):
           next_w = self.norm.weight
         else:
           next_w = None
-        h, normed = layer.forward_carry(h, normed, next_w, cos, sin, positions, kv, start_pos,
-                                        is_decode, seq_lens)
-      elif use_ckpt:
-        h = torch.utils.checkpoint.checkpoint(
-          layer, h, cos, sin, positions, kv, start_pos, is_decode, seq_lens,
-          use_reentrant=False)
+        h, normed = layer.forward_carry(h, normed, next_w, self.rope_cos, self.rope_sin, positions,
+                                        kv, start_pos, is_decode, seq_lens)
       else:
-        h = layer(h, cos, sin, positions, kv, start_pos, is_decode, seq_lens)
+        h = self._run_layer(layer, use_ckpt, h, positions, kv, start_pos, is_decode, seq_lens)
     if not self.shard.is_last_layer:
       return h
-    if last_only and h.shape[1] > 1:
-      h = h[:, -1:, :].contiguous()  # kernels require contiguous rows
-      normed = None
-    h = normed if normed is not None else self.norm(h)
+    last = self._last_rows(h, last_only)
+    h = normed if normed is not None and last is h else self.norm(last)  # normed is of the unsliced h
     if hasattr(self, "lm_head"):
       logits = self.lm_head(h)  # XotLinear: packed decode kernel when prepacked
     else:
       logits = ops.linear(h, self.head_weight().to(h.dtype))
-    if is_decode or last_only:
-      return logits[:, -1, :]
-    return logits
+    return self._pick(logits, is_decode, last_only)
 
 
 def hf_key_map(shard: Shard, cfg: ModelConfig):

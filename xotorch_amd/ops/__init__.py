@@ -94,6 +94,12 @@ def fuse_epilogue_enabled() -> bool:
   return os.getenv("XOT_FUSE_EPILOGUE", "1") != "0"
 
 
+def mfma_attn_enabled() -> bool:
+  """XOT_MFMA_ATTN (default 1, read per call): fragment-packed KV cache
+  copies and the MFMA attention kernels that stream them."""
+  return os.getenv("XOT_MFMA_ATTN", "1") == "1"
+
+
 def rope_apply(q, k, cos, sin, positions):
   """Standalone RoPE (training / oracle paths). On the GPU inference hot
   path RoPE is fused into rope_qkv_append — there is deliberately no
@@ -120,8 +126,7 @@ def rope_qkv_append(qkv, cos, sin, positions, k_cache, v_cache, n_heads: int, n_
 def attn_prefill(q, k_cache, v_cache, start_pos: int, s_len: int, kp=None, vp=None,
                  scale=None, softcap: float = 0.0, window: int = 0):
   if q.is_cuda and q.dtype == torch.bfloat16 and kp is not None and q.shape[3] == 128 \
-     and kp.dtype == torch.bfloat16 \
-     and os.getenv("XOT_MFMA_ATTN", "1") == "1" and _use_hip(q):
+     and kp.dtype == torch.bfloat16 and mfma_attn_enabled() and _use_hip(q):
     # causal flash-forward on matrix cores, streaming the MFMA-packed cache;
     # softcap/window run gemma2 semantics inside the same kernel (fp8-KV
     # mode keeps prefill on the plain bf16 cache via the sdpa path below)
@@ -155,7 +160,7 @@ def attn_decode(q, k_cache, v_cache, seq_len, kp=None, vp=None,
     if not isinstance(seq_len, torch.Tensor):
       seq_len = torch.full((q.shape[0],), int(seq_len), dtype=torch.int32, device=q.device)
     rep = q.shape[2] // k_cache.shape[1]
-    if kp is not None and rep <= 16 and os.getenv("XOT_MFMA_ATTN", "1") == "1":
+    if kp is not None and rep <= 16 and mfma_attn_enabled():
       return _hip.attn_decode_mfma(q, kp, vp, seq_len, k_cache.shape[2],
                                    scale or 0.0, softcap, window, k_scale, v_scale)
     if not softcap and not window and scale is None:
@@ -185,8 +190,8 @@ def geglu_packed(gu):
 
 # ---- GPU-only bindings: the decode GEMMs on prepacked weights (x [.., K]
 # bf16, 32..256 rows in multiples of 32; wp from pack_decode_weight[_fp8]) and
-# the MoE decode launches. No torch twin: models/linear.py and models/moe.py
-# decide when they run, and a missing extension is an error.
+# the MoE and MLA decode launches. No torch twin: models/linear.py, models/moe.py
+# and models/deepseek_v3.py decide when they run, and a missing extension is an error.
 
 def _gpu():
   if _load_hip() is None:
@@ -209,6 +214,12 @@ skinny_gemm_fp8 = _binding("skinny_gemm_fp8")          # (x8, sx, wp8, sw, E, N[
 moe_route = _binding("moe_route")
 moe_build = _binding("moe_build")      # (ids int32 [T, k], E, C): counting sort -> (gather_tok [E*C], inv_pos [T, k])
 moe_combine = _binding("moe_combine")  # (y [E*C, D], inv_pos, weights fp32) -> [T, D] bf16, deterministic
+# MLA (models/deepseek_v3.py) on the latent cache's packed copies (kp, vp; e4m3 with k_scale in fp8-KV mode)
+# (ckv, latent norm w, cos, sin, int32 positions, lat_c, rot_c, kp, vp, eps, interleave, k_scale | None): norm + rope + append
+mla_prep_append = _binding("mla_prep_append")
+# (q [B,S,H,qk], q_lat, cos, sin, int32 positions, nope, interleave, fp8) -> (q [B,H,576][, per-head scales when fp8])
+mla_q_prep = _binding("mla_q_prep")
+attn_decode_mla = _binding("attn_decode_mla")  # (q, kp, vp, seq_lens, scale, q_scale | None, k_scale | None) -> [B, H, lat]
 
 
 def _packed_epilogue(fn, x, wp, N, bias, epilogue):

@@ -24,11 +24,11 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
+from xotorch_amd import ops
 from xotorch_amd.engine.kvcache import ShardKVCache
-from xotorch_amd.models import model_class_for
+from xotorch_amd.models.build import build_shard_model
 from xotorch_amd.models.config import ModelConfig, config_from_hf
 from xotorch_amd.models.registry import builtin_config
-from xotorch_amd.models.weights import fast_random_init_gpu, random_init
 from xotorch_amd.parallel.comm import RingComm
 from xotorch_amd.parallel.partitioning import Partition, map_partitions_to_shards
 from xotorch_amd.shard import Shard
@@ -96,27 +96,7 @@ class RingPipeline:
     self.prev_rank = (rank - 1) % world
     self.comm = RingComm(device)
 
-    # --- model ---
-    # construct at the target dtype so to_empty materializes bf16 directly
-    # (fp32-then-cast would peak at 2x the weight bytes and leave the
-    # allocator's reserved pool at that level)
-    model_cls = model_class_for(self.cfg)
-    prev_dtype = torch.get_default_dtype()
-    torch.set_default_dtype(dtype)
-    try:
-      with torch.device("meta"):
-        model = model_cls(self.cfg, self.shard)
-    finally:
-      torch.set_default_dtype(prev_dtype)
-    model = model.to_empty(device=device)
-    model = model.to(dtype)
-    if device == "cuda" and self.cfg.dim >= 2048:
-      fast_random_init_gpu(model, seed)
-    else:
-      random_init(model, seed)
-    model.reset_rope()  # to_empty left the tables uninitialized
-    model.eval()
-    self.model = model
+    self.model = model = build_shard_model(self.cfg, self.shard, dtype, device, seed=seed, fast_init=True)
     if device == "cuda":
       # decode-GEMM weight prepack (memory permitting; KV caches below still
       # need room — reserve their size + headroom before packing greedily)
@@ -124,8 +104,7 @@ class RingPipeline:
         self.M * 2 * shards[rank].get_layer_count() * mb_batch * self.cfg.n_kv_heads
         * self.total_len * self.cfg.head_dim * (2 if dtype == torch.bfloat16 else 4)
       )
-      if self.cfg.head_dim == 128 and dtype == torch.bfloat16 \
-         and os.getenv("XOT_MFMA_ATTN", "1") == "1":
+      if self.cfg.head_dim == 128 and dtype == torch.bfloat16 and ops.mfma_attn_enabled():
         kv_bytes *= 2  # the MFMA-packed cache copies double KV residency
       torch.cuda.empty_cache()  # release init-time cached blocks so the
       # pack policy's mem_get_info reflects actually-usable HBM
@@ -133,10 +112,8 @@ class RingPipeline:
 
     # --- per-micro-batch state ---
     B = mb_batch
-    kv_heads, k_dim, v_dim = self.cfg.kv_cache_dims()
     self.caches = [
-      ShardKVCache(self.shard.get_layer_count(), B, kv_heads, self.total_len,
-                   k_dim, dtype, device, v_dim=v_dim)
+      ShardKVCache.for_config(self.cfg, self.shard.get_layer_count(), B, self.total_len, dtype, device)
       for _ in range(self.M)
     ]
     self.positions = [torch.zeros(1, dtype=torch.int32, device=device) for _ in range(self.M)]
@@ -221,13 +198,8 @@ class RingPipeline:
     outs = []
     for c0 in range(0, B, bc):
       c1 = min(c0 + bc, B)
-      sliced = []
-      for layer in self.caches[mb].caches:
-        if len(layer) > 2 and layer[2] is not None:
-          sliced.append((layer[0][c0:c1], layer[1][c0:c1], layer[2][c0:c1], layer[3][c0:c1]))
-        else:
-          sliced.append((layer[0][c0:c1], layer[1][c0:c1]))
-      outs.append(self.model(x[c0:c1], caches=sliced, positions=pos, start_pos=start_pos))
+      outs.append(self.model(x[c0:c1], caches=self.caches[mb].rows(c0, c1), positions=pos,
+                             start_pos=start_pos))
     return torch.cat(outs, dim=0)
 
   def prefill(self, prompts: Optional[List[torch.Tensor]] = None) -> RingStats:

@@ -46,9 +46,9 @@ import torch
 import torch.distributed as dist
 
 from xotorch_amd.engine.kvcache import ShardKVCache
+from xotorch_amd.models.build import build_shard_model
 from xotorch_amd.models.config import config_from_hf
 from xotorch_amd.models.registry import builtin_config, get_repo
-from xotorch_amd.models.weights import fast_random_init_gpu, load_shard_weights, random_init
 from xotorch_amd.parallel.comm import RingComm, init_distributed
 from xotorch_amd.parallel.ring import equal_ring_shards
 
@@ -96,29 +96,10 @@ class RingSlotWorker:
     self.cfg = config_from_hf(builtin_config(model_id) or {}, model_id)
     self.max_seq = min(self.max_seq, self.cfg.max_seq_len)
     self.shard = equal_ring_shards(model_id, self.cfg.n_layers, world)[rank]
-    from xotorch_amd.models import model_class_for
-    model_cls = model_class_for(self.cfg)
-    prev_dtype = torch.get_default_dtype()
-    torch.set_default_dtype(dtype)
-    try:
-      with torch.device("meta"):
-        model = model_cls(self.cfg, self.shard)
-    finally:
-      torch.set_default_dtype(prev_dtype)
-    model = model.to_empty(device=device).to(dtype)
-    if model_dir:
-      load_shard_weights(model, model_dir, device="cpu")
-      model = model.to(device)
-    elif device == "cuda" and self.cfg.dim >= 2048:
-      fast_random_init_gpu(model)
-    else:
-      random_init(model)
-    model.reset_rope()
-    model.eval()
-    self.model = model
-    heads, k_dim, v_dim = self.cfg.kv_cache_dims()
-    self.cache = ShardKVCache(self.shard.get_layer_count(), slots, heads,
-                              self.max_seq, k_dim, dtype, device, v_dim=v_dim)
+    self.model = model = build_shard_model(self.cfg, self.shard, dtype, device,
+                                           model_dir=model_dir, fast_init=True)
+    self.cache = ShardKVCache.for_config(self.cfg, self.shard.get_layer_count(), slots,
+                                         self.max_seq, dtype, device)
     if device == "cuda":
       torch.cuda.empty_cache()
       model.pack_decode_weights(reserve_bytes=8 << 30)
@@ -229,11 +210,7 @@ class RingSlotWorker:
   # ---------------- prefill (chunked through the ring) ----------------
 
   def _slot_caches(self, slot: int):
-    out = []
-    for layer in self.cache.caches:
-      sl = tuple(t[slot:slot + 1] if t is not None else None for t in layer)
-      out.append(type(layer)(*sl) if hasattr(layer, "_fields") else sl)
-    return out
+    return self.cache.rows(slot, slot + 1)
 
   def _prefill_chunk(self, slot: int, caches, tokens, c0: int, c1: int,
                      plen: int) -> Optional[int]:
