@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Decode-GEMM shape race: hipBLASLt (TunableOp) vs packed-LDS (v2) vs
-packed-xreg (v3) on the 70B/8B decode shapes at M=64/128/256.
+"""Decode-GEMM shape race: hipBLASLt (TunableOp) vs packed-LDS (v2, on its
+128-row and its 256-row weight tile) vs packed-xreg (v3) on the 70B/8B decode
+shapes at M=64/128/256. The 256-row tile exists for M >= 128 and N % 256 == 0;
+elsewhere XOT_SKINNY_BN=256 runs the 128-row tile and the two columns agree.
 
 Run on a GPU box:
   python tools/gemm_decode_bench.py [--check-only]
@@ -54,7 +56,7 @@ def main():
   assert hip is not None, "HIP extension missing"
   dev = "cuda"
   torch.manual_seed(7)
-  print(f"{'shape':<10} {'M':>4} {'blaslt':>9} {'packed':>9} {'pk-bk64':>9} {'xreg':>9}  best (TB/s of weight stream)")
+  print(f"{'shape':<10} {'M':>4} {'blaslt':>9} {'pk-bn128':>9} {'pk-bn256':>9} {'pk-bk64':>9} {'xreg':>9}  best (TB/s of weight stream)")
   for name, N, K in SHAPES:
     w = (torch.randn(N, K, device=dev) / K**0.5).to(torch.bfloat16)
     wp = ops.pack_decode_weight(w)
@@ -72,15 +74,20 @@ def main():
         print(f"{name:<10} {M:>4} ok")
         continue
       t_bl = time_us(lambda: torch.nn.functional.linear(x, w))
+      os.environ["XOT_SKINNY_BN"] = "128"
       t_pk = time_us(lambda: hip.skinny_gemm_packed(x, wp, N, None))
+      os.environ["XOT_SKINNY_BN"] = "256"
+      t_pw = time_us(lambda: hip.skinny_gemm_packed(x, wp, N, None))
+      del os.environ["XOT_SKINNY_BN"]
       os.environ["XOT_SKINNY_BK64"] = "1"
       t_p64 = time_us(lambda: hip.skinny_gemm_packed(x, wp, N, None))
       del os.environ["XOT_SKINNY_BK64"]
       t_xr = time_us(lambda: hip.skinny_gemm_packed_xreg(x, wp, N, None))
-      best = min(t_bl, t_pk, t_p64, t_xr)
+      best = min(t_bl, t_pk, t_pw, t_p64, t_xr)
       tbps = wbytes / best / 1e6
-      win = {t_bl: "blaslt", t_pk: "packed", t_p64: "pk-bk64", t_xr: "xreg"}[best]
-      print(f"{name:<10} {M:>4} {t_bl:>9.1f} {t_pk:>9.1f} {t_p64:>9.1f} {t_xr:>9.1f}  {win} {tbps:.2f} TB/s")
+      win = {t_bl: "blaslt", t_pk: "pk-bn128", t_pw: "pk-bn256", t_p64: "pk-bk64", t_xr: "xreg"}[best]
+      print(f"{name:<10} {M:>4} {t_bl:>9.1f} {t_pk:>9.1f} {t_pw:>9.1f} {t_p64:>9.1f} {t_xr:>9.1f}  {win} {tbps:.2f} TB/s",
+            flush=True)
     del w, wp
     torch.cuda.empty_cache()
 

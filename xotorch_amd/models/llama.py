@@ -252,20 +252,39 @@ class DecoderLayer(nn.Module):
     return ops.add_rmsnorm(self.mlp(normed), h, next_norm_w, self.eps)
 
 
+def pack_group_partial(grp, bytes_per: int, reserve_bytes: int, free_bytes) -> int:
+  """Pack grp's modules in order while one more packed copy still leaves
+  `reserve_bytes` free; free_bytes() is read again before every module.
+  Modules without a packed copy run hipBLASLt (XotLinear._gemm), so a
+  half-packed group works. Returns how many modules were packed."""
+  n = 0
+  for m in grp:
+    if m.weight.numel() * bytes_per + reserve_bytes > free_bytes():
+      break
+    m.pack_decode()
+    n += 1
+  return n
+
+
 def pack_decode_weights(model, reserve_bytes: int) -> int:
   """Prepack decode-GEMM weights (second copy in MFMA fragment order) in
   descending measured-win order — down_proj (hipBLASLt ~3 TB/s at K=28672
   vs 5.4 packed), lm_head, gate_up, qkv/o — greedily while at least
   `reserve_bytes` of HBM stay free (KV caches and activations are usually
-  allocated before this is called). Returns bytes packed. Policy override:
+  allocated before this is called). A group that does not fit as a whole is
+  packed module by module as far as it fits (pack_group_partial); the rest
+  of its modules stay on hipBLASLt. Returns bytes packed. Policy override:
   XOT_PACK=none|down|all."""
   mode = os.getenv("XOT_PACK", "auto")
   if mode == "none" or not torch.cuda.is_available():
     return 0
   groups: List[List[XotLinear]] = [[], [], [], []]
+  experts = set()
   for name, mod in model.named_modules():
     if not isinstance(mod, XotLinear) or not mod.packable():
       continue
+    if "experts." in name:
+      experts.add(mod)
     if "down_proj" in name:
       # the packed kernel wins when the split-K grid still fills the chip
       # (>= ~1.5 blocks/CU); small-N down projections stay on hipBLASLt.
@@ -287,15 +306,19 @@ def pack_decode_weights(model, reserve_bytes: int) -> int:
     groups = groups[:3]
   packed = 0
   debug = os.getenv("XOT_DEBUG", "0") != "0"
+  free_bytes = lambda: torch.cuda.mem_get_info()[0]
   for gi, grp in enumerate(groups):
     if not grp:
       continue
     bytes_per = 1 if ops.fp8_gemm_enabled() else 2
     need = sum(m.weight.numel() * bytes_per for m in grp)
-    free, _ = torch.cuda.mem_get_info()
+    free = free_bytes()
     if need + reserve_bytes > free:
+      # MoE experts pack all or none: the grouped stack needs every expert
+      n = 0 if any(m in experts for m in grp) else pack_group_partial(grp, bytes_per, reserve_bytes, free_bytes)
+      packed += sum(m.weight.numel() * bytes_per for m in grp[:n])
       if debug:
-        print(f"[xot] pack group {gi}: skip (need {need>>20} MiB + reserve "
+        print(f"[xot] pack group {gi}: packed {n} of {len(grp)} modules (need {need>>20} MiB + reserve "
               f"{reserve_bytes>>20} MiB > free {free>>20} MiB)", flush=True)
       continue
     for m in grp:

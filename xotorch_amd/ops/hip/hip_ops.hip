@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <cstring>
 #include <vector>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -1840,8 +1841,16 @@ DEVINL ushort8 skinny_stage_load(const unsigned short* p, long long K) {
 // Mixtral-class decode each expert e (blockIdx.y) computes its own
 // [C, N] = [C, K] @ Wp_e^T over a fixed per-expert token capacity C — one
 // launch covers every expert, weights stream from the stacked prepack.
-template <int MT, bool SPLIT, int BK, bool SWIGLU = false>
-__global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
+//
+// NW = waves per workgroup = 32-row weight tiles per workgroup. NW = 4 is the
+// 128-row tile with one LDS image and two barriers per K-step. NW = 8 (MT >= 4
+// only) is the 256-row tile: all 8 waves share one staged X image, so the
+// staged X bytes and the staging work per weight byte halve, and the image is
+// double-buffered so a K-step costs one barrier. Each wave's A stream, its
+// accumulators and its MFMA order are the same in both, and the launcher keeps
+// nsplit and kc, so both give the same bits.
+template <int MT, bool SPLIT, int BK, bool SWIGLU = false, int NW = 4>
+__global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(
     const unsigned short* __restrict__ Wp, const unsigned short* __restrict__ X,
     unsigned short* __restrict__ Y, float* __restrict__ P,
     const unsigned short* __restrict__ bias,
@@ -1853,7 +1862,10 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
   if (!SWIGLU) ldx = K;
   constexpr int BKC = BK / 16;   // MFMA k-chunks (A fragments) per K-step
   constexpr int XROW = BK + 8;   // padded LDS row stride (elems): conflict-free b128
-  const int ntiles = N >> 7;
+  constexpr int NT = NW * 64;    // threads
+  constexpr int XBUFS = NW == 8 ? 2 : 1;  // LDS images (double-buffered on the wide tile)
+  constexpr int XIMG = MT * 32 * XROW;    // elems per image
+  const int ntiles = N / (NW * 32);
   const int tile = blockIdx.x % ntiles;
   const int split = blockIdx.x / ntiles;
   // grouped mode: expert blockIdx.y owns rows [e*MT*32, (e+1)*MT*32) of X/Y
@@ -1868,62 +1880,75 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
   const int wv = threadIdx.x >> 6;
   const int tid = threadIdx.x;
 
-  __shared__ unsigned short xs[MT * 32 * XROW];
+  __shared__ unsigned short xs[XBUFS * XIMG];
 
   floatx16 acc[MT];
 #pragma unroll
   for (int t = 0; t < MT; ++t) acc[t] = (floatx16)(0.f);
 
   // A stream: packed row for this wave's 32-n tile
-  const int n32 = tile * 4 + wv;
+  const int n32 = tile * NW + wv;
   const unsigned short* wp = Wp + ((size_t)n32 * (K >> 4) + (k0 >> 4)) * 512 + (size_t)lane * 8;
-  // X stage: thread tid covers 16 B pieces p = tid + i*256 (coalesced);
+  // X stage: thread tid covers 16 B pieces p = tid + i*NT (coalesced);
   // row = p / (BK/8), piece-in-row q = p % (BK/8); global [M, K] row-major.
-  constexpr int PPT = MT * BK / 64;  // pieces per thread per step
+  constexpr int ROWS_PER_I = NT * 8 / BK;  // rows advanced per i (NT threads)
+  constexpr int PPT = (MT * 32 + ROWS_PER_I - 1) / ROWS_PER_I;  // pieces per thread per step
+  // odd MT on the wide tile at BK=64: the last piece covers only half the
+  // threads (rows past MT*32 are neither loaded nor stored)
+  constexpr bool RAGGED = (MT * 32) % ROWS_PER_I != 0;
+  const bool tail_ok = !RAGGED || tid / (BK / 8) + (PPT - 1) * ROWS_PER_I < MT * 32;
   const int nsteps = (int)((k1 - k0) >> (BK == 64 ? 6 : 7));
   ushort8 xv[PPT];
   bf16x8 a_buf[2][BKC];
-  // per-thread staging base + uniform per-piece offsets: piece p = tid+i*256
+  // per-thread staging base + uniform per-piece offsets: piece p = tid+i*NT
   // has row = tid/(BK/8) + i*ROWS_PER_I and column-piece q = tid%(BK/8), so
   // one VGPR pointer plus SGPR/immediate strides replaces the old per-piece
   // pointer arrays (saves ~10 VGPRs -> a wave/SIMD at MT=4)
-  constexpr int ROWS_PER_I = 2048 / BK;  // rows advanced per i (256 threads)
   const unsigned short* xpb = X + k0 + (size_t)(tid / (BK / 8)) * ldx + (tid % (BK / 8)) * 8;
   const int xsb = (tid / (BK / 8)) * XROW + (tid % (BK / 8)) * 8;
   const long long xstride_i = (long long)ROWS_PER_I * ldx;
+
+#define SGP_XLOAD(STEP)                                                                        \
+  _Pragma("unroll")                                                                            \
+  for (int i = 0; i < PPT; ++i)                                                                \
+    if (i < PPT - 1 || tail_ok)                                                                \
+      xv[i] = skinny_stage_load<SWIGLU>(xpb + i * xstride_i + (size_t)(STEP) * BK, K);
+#define SGP_XSTORE(IMG)                                                                        \
+  _Pragma("unroll")                                                                            \
+  for (int i = 0; i < PPT; ++i)                                                                \
+    if (i < PPT - 1 || tail_ok)                                                                \
+      *(ushort8*)(xs + (IMG) * XIMG + xsb + i * ROWS_PER_I * XROW) = xv[i];
 
   // prologue: stage step 0, preload A(0) and A(1).  The W stream is read
   // exactly once per launch -> non-temporal (L1-bypass) loads; depth-2
   // prefetch keeps 2*BK*32n*2B per wave in flight across staging barriers.
   const unsigned short* wp1 = (nsteps > 1) ? wp + BKC * 512 : wp;  // clamp: no OOB at nsteps==1
-#pragma unroll
-  for (int i = 0; i < PPT; ++i) xv[i] = skinny_stage_load<SWIGLU>(xpb + i * xstride_i, K);
+  SGP_XLOAD(0)
 #pragma unroll
   for (int u = 0; u < BKC; ++u) {
     a_buf[0][u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wp + u * 512));
     a_buf[1][u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wp1 + u * 512));
   }
   wp += 2 * BKC * 512;
-#pragma unroll
-  for (int i = 0; i < PPT; ++i) *(ushort8*)(xs + xsb + i * ROWS_PER_I * XROW) = xv[i];
+  SGP_XSTORE(0)
   __syncthreads();
 
   // NOTE: the A double-buffer index must be a compile-time constant — a
   // dynamic a_buf[s & 1] spills the whole array to scratch (measured 25-40x).
+  // Step s reads LDS image BUF (= s & 1) when double-buffered and fills the
+  // other one for step s+1: the barrier that ended step s-1 is what lets every
+  // wave overwrite the image step s-1 read, so one barrier per step is enough.
 #define SGP_STEP(BUF)                                                                          \
   {                                                                                            \
+    constexpr int RD = XBUFS == 2 ? (BUF) : 0;                                                 \
     const bool last = (s == nsteps - 1);                                                       \
-    if (!last) {                                                                               \
-      _Pragma("unroll")                                                                        \
-      for (int i = 0; i < PPT; ++i)                                                            \
-        xv[i] = skinny_stage_load<SWIGLU>(xpb + i * xstride_i + (size_t)(s + 1) * BK, K);      \
-    }                                                                                          \
+    if (!last) { SGP_XLOAD(s + 1) }                                                            \
     _Pragma("unroll")                                                                          \
     for (int u = 0; u < BKC; ++u) {                                                            \
       _Pragma("unroll")                                                                        \
       for (int t = 0; t < MT; ++t) {                                                           \
         const bf16x8 b = *reinterpret_cast<const bf16x8*>(                                     \
-            xs + t * 32 * XROW + (lane & 31) * XROW + u * 16 + (lane >> 5) * 8);               \
+            xs + RD * XIMG + t * 32 * XROW + (lane & 31) * XROW + u * 16 + (lane >> 5) * 8);   \
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_buf[BUF][u], b, acc[t], 0, 0, 0);   \
       }                                                                                        \
     }                                                                                          \
@@ -1934,9 +1959,8 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
       wp += BKC * 512;                                                                         \
     }                                                                                          \
     if (!last) {                                                                               \
-      __syncthreads();                                                                         \
-      _Pragma("unroll")                                                                        \
-      for (int i = 0; i < PPT; ++i) *(ushort8*)(xs + xsb + i * ROWS_PER_I * XROW) = xv[i];     \
+      if (XBUFS == 1) __syncthreads();                                                         \
+      SGP_XSTORE(XBUFS == 2 ? 1 - (BUF) : 0)                                                   \
       __syncthreads();                                                                         \
     }                                                                                          \
   }
@@ -1950,10 +1974,13 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
   }
   if (s < nsteps) SGP_STEP(0);
 #undef SGP_STEP
+#undef SGP_XLOAD
+#undef SGP_XSTORE
 
   // rows_total spans all experts
   skinny_store_acc<MT, SPLIT>(acc, Y, P, bias, N, split, gridDim.y * MT * 32,
-                              e * MT * 32 + (lane & 31), tile * 128 + wv * 32 + 4 * (lane >> 5));
+                              e * MT * 32 + (lane & 31),
+                              tile * (NW * 32) + wv * 32 + 4 * (lane >> 5));
 }
 
 // ---------------------------------------------------------------------------
@@ -2922,14 +2949,41 @@ struct SkinnyEpilogue {
   }
 };
 
+// The packed kernel's weight tile per workgroup for this call: 256 rows (8
+// waves sharing one staged X image) or 128. The wide tile needs MT >= 4 (at
+// smaller M the staged X is a small share of the load traffic and the 128-row
+// grid fills the chip better) and N % 256 == 0. Measured default (docs/PERF.md,
+// 256-row tile): at rows < 256 the wide tile wins where a workgroup streams
+// kc >= 2048 of K (gate_up, down, lm_head: -4..-11 %) and loses on shorter
+// streams (qkv: +14..+18 %), where the 128-row tile at BK=64 keeps three
+// workgroups per CU resident against one wide one. At rows = 256 the 128-row
+// tile is down to one 4-wave workgroup per CU and the wide tile wins
+// (-11..-31 %) unless its grid covers under half of the 256 CUs. MT 5..7 are
+// not measured and follow MT = 4. XOT_SKINNY_BN=128|256 overrides the default
+// and is read per call (the GEMM race tool and the equality tests toggle it);
+// an ineligible shape stays on 128 either way.
+static bool skinny_wide_tile(long long rows, long long N, long long E, const SkinnyPlan& p) {
+  if (rows < 128 || N % 256 != 0) return false;
+  const char* bn = getenv("XOT_SKINNY_BN");
+  if (bn != nullptr) {
+    CHK(strcmp(bn, "128") == 0 || strcmp(bn, "256") == 0);
+    return bn[0] == '2';
+  }
+  if (rows < 256) return p.kc >= 2048;
+  return (long long)(p.ntiles / 2) * p.nsplit * E >= 128;
+}
+
 // Shared tail of every launcher: validate bias, allocate y (and the fp32
 // partials P [nsplit, E*rows, N] when split), launch the kernel that
-// `launch(mt, split, bk, L)` names with MT / SPLIT / BK as compile-time
-// constants, then combine. rows = rows per expert. With an epilogue the row
-// kernel takes the combine's place (split) or follows the GEMM's bf16 y
-// (unsplit); its results are left in *epi and the returned y is undefined
-// when split.
-template <bool HAS_BK128, class F>
+// `launch(mt, split, bk, nw, L)` names with MT / SPLIT / BK / NW as
+// compile-time constants, then combine. rows = rows per expert. PACKED = the
+// launcher runs skinny_gemm_packed_kernel, which has the BK=128 staging and
+// the 256-row tile (NW = 8); the plan is made from 128-row tiles either way
+// and the wide tile only halves grid.x, so P and the combine do not change.
+// With an epilogue the row kernel takes the combine's place (split) or
+// follows the GEMM's bf16 y (unsplit); its results are left in *epi and the
+// returned y is undefined when split.
+template <bool PACKED, class F>
 static torch::Tensor skinny_run(const torch::Tensor& x, at::IntArrayRef ysizes, long long rows,
                                 long long N, long long K, long long E,
                                 const c10::optional<torch::Tensor>& bias, int k_align, F&& launch,
@@ -2939,23 +2993,33 @@ static torch::Tensor skinny_run(const torch::Tensor& x, at::IntArrayRef ysizes, 
     CHK(bias->is_contiguous() && bias->dtype() == torch::kBFloat16 && bias->numel() == N);
     bptr = (const unsigned short*)bias->data_ptr();
   }
-  const SkinnyPlan p = skinny_plan(N, K, E, k_align, HAS_BK128);
+  const SkinnyPlan p = skinny_plan(N, K, E, k_align, PACKED);
   const bool is_split = p.nsplit > 1;
+  const bool wide = PACKED && skinny_wide_tile(rows, N, E, p);
   torch::Tensor y;
   if (!(epi && is_split)) y = torch::empty(ysizes, x.options().dtype(torch::kBFloat16));
   torch::Tensor P;
   if (is_split)
     P = torch::empty({p.nsplit, (long)(E * rows), (long)N}, x.options().dtype(torch::kFloat32));
-  const SkinnyLaunch L{dim3(p.ntiles * p.nsplit, (unsigned)E), cur_stream(),
+  const SkinnyLaunch L{dim3((wide ? p.ntiles / 2 : p.ntiles) * p.nsplit, (unsigned)E), cur_stream(),
                        is_split ? nullptr : (unsigned short*)y.data_ptr(),
                        is_split ? P.data_ptr<float>() : nullptr,
                        is_split ? nullptr : bptr, p.kc, p.nsplit};
   dispatch_1to8((int)(rows / 32), "skinny GEMM: MT", [&](auto mt) {
-    auto with_split = [&](auto split) {
-      if constexpr (HAS_BK128) {
-        if (p.bk128) return launch(mt, split, IntC<128>{}, L);
+    auto with_bk = [&](auto split, auto bk) {
+      if constexpr (PACKED && mt.value >= 4) {
+        // MT >= 7 on the wide tile stages BK=64: with two BK=128 images in
+        // flight the allocator spills (76-224 B/lane of scratch). Same bits,
+        // the k order within a split does not depend on BK.
+        if (wide) return launch(mt, split, IntC<(mt.value >= 7 ? 64 : bk.value)>{}, IntC<8>{}, L);
       }
-      launch(mt, split, IntC<64>{}, L);
+      launch(mt, split, bk, IntC<4>{}, L);
+    };
+    auto with_split = [&](auto split) {
+      if constexpr (PACKED) {
+        if (p.bk128) return with_bk(split, IntC<128>{});
+      }
+      with_bk(split, IntC<64>{});
     };
     if (is_split) with_split(std::true_type{}); else with_split(std::false_type{});
   });
@@ -2986,7 +3050,7 @@ torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w,
   auto sizes = x.sizes().vec();
   sizes.back() = N;
   return skinny_run<false>(x, sizes, M, N, K, 1, bias, 16,
-                           [&](auto mt, auto split, auto, const SkinnyLaunch& L) {
+                           [&](auto mt, auto split, auto, auto, const SkinnyLaunch& L) {
     hipLaunchKernelGGL((skinny_gemm_kernel<mt.value, split.value>), L.grid, dim3(256), 0, L.stream,
                        (const unsigned short*)w.data_ptr(), (const unsigned short*)x.data_ptr(),
                        L.Y, L.P, L.bias, N, K, L.kc, L.nsplit);
@@ -3007,9 +3071,9 @@ static torch::Tensor skinny_gemm_packed_impl(const torch::Tensor& x, const torch
   auto sizes = x.sizes().vec();
   sizes.back() = (long)N;
   return skinny_run<true>(x, sizes, M, N, K, 1, bias, 64,
-                          [&](auto mt, auto split, auto bk, const SkinnyLaunch& L) {
-    hipLaunchKernelGGL((skinny_gemm_packed_kernel<mt.value, split.value, bk.value>),
-                       L.grid, dim3(256), 0, L.stream,
+                          [&](auto mt, auto split, auto bk, auto nw, const SkinnyLaunch& L) {
+    hipLaunchKernelGGL((skinny_gemm_packed_kernel<mt.value, split.value, bk.value, false, nw.value>),
+                       L.grid, dim3(nw.value * 64), 0, L.stream,
                        (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(),
                        L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit);
   }, epi);
@@ -3044,7 +3108,7 @@ torch::Tensor skinny_gemm_packed_xreg(torch::Tensor x, torch::Tensor wp, int64_t
   auto sizes = x.sizes().vec();
   sizes.back() = (long)N;
   return skinny_run<false>(x, sizes, M, N, K, 1, bias, 64,
-                           [&](auto mt, auto split, auto, const SkinnyLaunch& L) {
+                           [&](auto mt, auto split, auto, auto, const SkinnyLaunch& L) {
     hipLaunchKernelGGL((skinny_gemm_packed_xreg_kernel<mt.value, split.value>),
                        L.grid, dim3(256), 0, L.stream,
                        (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(),
@@ -3070,9 +3134,9 @@ static torch::Tensor skinny_gemm_packed_swiglu_impl(const torch::Tensor& gu, con
   sizes.back() = (long)N;
   const long long ldx = 2 * K;
   return skinny_run<true>(gu, sizes, M, N, K, 1, bias, 64,
-                          [&](auto mt, auto split, auto bk, const SkinnyLaunch& L) {
-    hipLaunchKernelGGL((skinny_gemm_packed_kernel<mt.value, split.value, bk.value, true>),
-                       L.grid, dim3(256), 0, L.stream,
+                          [&](auto mt, auto split, auto bk, auto nw, const SkinnyLaunch& L) {
+    hipLaunchKernelGGL((skinny_gemm_packed_kernel<mt.value, split.value, bk.value, true, nw.value>),
+                       L.grid, dim3(nw.value * 64), 0, L.stream,
                        (const unsigned short*)wp.data_ptr(), (const unsigned short*)gu.data_ptr(),
                        L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit, ldx);
   }, epi);
@@ -3117,9 +3181,9 @@ torch::Tensor skinny_gemm_grouped(torch::Tensor x, torch::Tensor wp, int64_t E, 
   CHK(C >= 32 && C <= 256 && C % 32 == 0);
   CHK(N % 128 == 0 && K % 64 == 0 && E >= 1 && E <= 256);
   return skinny_run<true>(x, {(long)E, (long)C, (long)N}, C, N, K, E, c10::nullopt, 64,
-                          [&](auto mt, auto split, auto bk, const SkinnyLaunch& L) {
-    hipLaunchKernelGGL((skinny_gemm_packed_kernel<mt.value, split.value, bk.value>),
-                       L.grid, dim3(256), 0, L.stream,
+                          [&](auto mt, auto split, auto bk, auto nw, const SkinnyLaunch& L) {
+    hipLaunchKernelGGL((skinny_gemm_packed_kernel<mt.value, split.value, bk.value, false, nw.value>),
+                       L.grid, dim3(nw.value * 64), 0, L.stream,
                        (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(),
                        L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit);
   });
@@ -3154,7 +3218,7 @@ torch::Tensor skinny_gemm_fp8(torch::Tensor x8, torch::Tensor sx, torch::Tensor 
   CHK(M >= 32 && M <= 256 && M % 32 == 0);
   CHK(N % 128 == 0 && K % 64 == 0 && sw.numel() == E * N && sx.numel() == E * M);
   return skinny_run<false>(x8, {(long)(E * M), (long)N}, M, N, K, E, bias, 64,
-                           [&](auto mt, auto split, auto, const SkinnyLaunch& L) {
+                           [&](auto mt, auto split, auto, auto, const SkinnyLaunch& L) {
     hipLaunchKernelGGL((skinny_gemm_fp8_kernel<mt.value, split.value>),
                        L.grid, dim3(256), 0, L.stream,
                        (const unsigned char*)wp8.data_ptr(), (const unsigned char*)x8.data_ptr(),
