@@ -4,13 +4,14 @@ Standard layout [B, KVH, T, hd]: each (b, kv_head) has T contiguous rows of
 hd elements (256 B at hd=128 bf16) — prefill attention (sdpa) and the VALU
 decode kernel stream rows with coalesced 16 B/lane loads.
 
-MFMA layout (GPU, hd=128): a second copy of K and V pre-shuffled into
-v_mfma_f32_16x16x32_bf16 B-fragment order so the MFMA flash-decoding kernel
-streams the cache with fully-coalesced 1 KB wave loads:
-  K_packed [B, KVH, T32/16, 4, 64, 8]   (16-position x 32-hd-chunk tiles)
-  V_packed [B, KVH, 8, T32/32, 64, 8]   (32-position x 16-hd-column tiles)
+MFMA layout (GPU, hd in ops.PACKED_HEAD_DIMS = 128 or 256): a second copy of K
+and V pre-shuffled into v_mfma_f32_16x16x32_bf16 B-fragment order so the MFMA
+attention kernels stream the cache with fully-coalesced 1 KB wave loads:
+  K_packed [B, KVH, T32/16, hd/32, 64, 8]   (16-position x 32-hd-chunk tiles)
+  V_packed [B, KVH, hd/16, T32/32, 64, 8]   (32-position x 16-hd-column tiles)
 (T32 = capacity rounded up to 32; both copies are appended by the fused
-rope_qkv_append kernel.)  The reference's equivalent is torchtune's per-layer
+rope_qkv_append kernel. In fp8-KV mode they are e4m3 bytes with per-row
+scales [B, KVH, T32], whatever the head dim.)  The reference's equivalent is torchtune's per-layer
 cache setup (/root/reference/xotorch/inference/torch/sharded_inference_engine.py:71-82).
 """
 from __future__ import annotations
@@ -26,8 +27,8 @@ from xotorch_amd import ops
 class LayerKV(NamedTuple):
   k: torch.Tensor
   v: torch.Tensor
-  kp: Optional[torch.Tensor] = None  # MFMA-packed K (cuda, hd=128; bf16 or e4m3 bytes)
-  vp: Optional[torch.Tensor] = None  # MFMA-packed V
+  kp: Optional[torch.Tensor] = None  # MFMA-packed K (cuda, hd 128 or 256; bf16 or e4m3 bytes)
+  vp: Optional[torch.Tensor] = None  # MFMA-packed V (same head dims and dtype as kp)
   ksc: Optional[torch.Tensor] = None  # fp8 mode: per-row K scales [B, KVH, T32]
   vsc: Optional[torch.Tensor] = None  # fp8 mode: per-row V scales
 
@@ -54,10 +55,11 @@ class ShardKVCache:
     # (kp, vp) and of the fp8 mode's per-row scale tensors, or none (plain)
     packed = (str(device).startswith("cuda") and dtype == torch.bfloat16
               and ops.mfma_attn_enabled())
-    if packed and head_dim == 128 and vd == 128:
-      # GQA: 16-position x 32-hd-chunk K tiles, 32-position x 16-hd-column V tiles
-      kp_shape = (batch, n_kv_heads, t32 // 16, 4, 64, 8)
-      vp_shape = (batch, n_kv_heads, 8, t32 // 32, 64, 8)
+    if packed and vd == head_dim and ops.gqa_packed_kv(head_dim, dtype):
+      # GQA (head_dim in ops.PACKED_HEAD_DIMS): 16-position x 32-hd-chunk K
+      # tiles, 32-position x 16-hd-column V tiles
+      kp_shape = (batch, n_kv_heads, t32 // 16, head_dim // 32, 64, 8)
+      vp_shape = (batch, n_kv_heads, head_dim // 16, t32 // 32, 64, 8)
       scale_shapes = [(batch, n_kv_heads, t32)] * 2
     elif packed and n_kv_heads == 1 and head_dim == 512 and vd == 64:
       # MLA latent cache (k = 512-dim latent, v = 64-dim roped shared key,

@@ -15,9 +15,11 @@ On MI355X the family runs the SAME CDNA4 kernel path as llama: fused qkv
 XotLinear GEMMs (packed skinny kernels), the fused RoPE+KV-append kernel
 into the MFMA-packed cache, MFMA flash attention with softcap/window flags
 (hip_ops.hip attn_*_mfma), gemma RMSNorm via the HIP rmsnorm kernel's
-w_bias=1 mode, and a packed GeGLU kernel. head_dim must be 128 for the
-MFMA attention (gemma2-27b); other dims fall back to the eager oracle path
-(also the CPU path, validated against transformers' Gemma2ForCausalLM).
+w_bias=1 mode, and a packed GeGLU kernel. The MFMA attention takes head_dim
+128 (gemma2-27b) and 256 (gemma2-9b); with an fp8 packed cache, prefill reads
+the plain bf16 cache instead (ops.attn_prefill), at either head dim. Other
+dims take the eager oracle path (also the CPU path, validated against
+transformers' Gemma2ForCausalLM).
 
 Shard semantics match ShardedModel: first shard owns the (scaled) embedding,
 last owns the final norm + tied head; caches are the engine's LayerKV pairs.
@@ -46,7 +48,7 @@ def _softcap(x: torch.Tensor, cap: float) -> torch.Tensor:
 
 def _use_mfma(x: torch.Tensor, hd: int, kv) -> bool:
   return (
-    x.is_cuda and x.dtype == torch.bfloat16 and hd == 128
+    x.is_cuda and x.dtype == torch.bfloat16 and hd in ops.PACKED_HEAD_DIMS
     and kv.kp is not None and ops.hip_available()
   )
 
@@ -87,7 +89,7 @@ class Gemma2Attention(nn.Module):
         out = ops.attn_prefill(q, k_cache, v_cache, start_pos, S, kv.kp, kv.vp,
                                scale=self.scale, softcap=cap, window=self.window)
       return self.o_proj(out.reshape(B, S, H * hd))
-    # eager oracle path (CPU / hd != 128): split the fused projection
+    # eager oracle path (CPU / hd outside ops.PACKED_HEAD_DIMS): split the fused projection
     if start_pos < 0:  # ring/serve decode contract: derive from positions
       out = ragged_decode_rows(self, x, cos, sin, positions, kv, is_decode)
       if out is not None:

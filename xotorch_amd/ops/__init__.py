@@ -100,6 +100,17 @@ def mfma_attn_enabled() -> bool:
   return os.getenv("XOT_MFMA_ATTN", "1") == "1"
 
 
+# head dims the fragment-packed GQA cache copies, the fused append into them
+# and the MFMA attention kernels are built for (hip_ops.hip GQA_PACKED_HD)
+PACKED_HEAD_DIMS = (128, 256)
+
+
+def gqa_packed_kv(head_dim: int, dtype: torch.dtype) -> bool:
+  """Whether a GPU GQA cache of this head dim and dtype carries the packed
+  second copies of K and V, which double its residency."""
+  return head_dim in PACKED_HEAD_DIMS and dtype == torch.bfloat16 and mfma_attn_enabled()
+
+
 def rope_apply(q, k, cos, sin, positions):
   """Standalone RoPE (training / oracle paths). On the GPU inference hot
   path RoPE is fused into rope_qkv_append — there is deliberately no
@@ -125,7 +136,7 @@ def rope_qkv_append(qkv, cos, sin, positions, k_cache, v_cache, n_heads: int, n_
 
 def attn_prefill(q, k_cache, v_cache, start_pos: int, s_len: int, kp=None, vp=None,
                  scale=None, softcap: float = 0.0, window: int = 0):
-  if q.is_cuda and q.dtype == torch.bfloat16 and kp is not None and q.shape[3] == 128 \
+  if q.is_cuda and q.dtype == torch.bfloat16 and kp is not None and q.shape[3] in PACKED_HEAD_DIMS \
      and kp.dtype == torch.bfloat16 and mfma_attn_enabled() and _use_hip(q):
     # causal flash-forward on matrix cores, streaming the MFMA-packed cache;
     # softcap/window run gemma2 semantics inside the same kernel (fp8-KV
@@ -133,7 +144,7 @@ def attn_prefill(q, k_cache, v_cache, start_pos: int, s_len: int, kp=None, vp=No
     return _hip.attn_prefill_mfma(q, kp, vp, start_pos, scale or 0.0, softcap, window)
   if q.is_cuda and not softcap and not window:
     # fallback: sdpa (rocm flash/mem-efficient backends) in model dtype with
-    # native GQA — hd != 128 or unpacked-cache path
+    # native GQA — hd outside PACKED_HEAD_DIMS or unpacked-cache path
     import torch.nn.functional as F
     B, S, H, hd = q.shape
     total = start_pos + s_len

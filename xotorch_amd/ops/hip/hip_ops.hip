@@ -79,12 +79,16 @@ DEVINL float wave_max(float v) {
 // what one v_mfma_f32_16x16x32 B operand reads: the attention kernels stream
 // it lane-linearly (lane * 8), one coalesced wave load per fragment.
 //   K image of a head: [pos>>4][d>>5][lane][d&7],  lane = ((d&31)>>3)*16 + (pos&15)
-//     a 16-position tile holds dims/32 fragments: 4 for GQA hd=128, 18 for MLA
+//     a 16-position tile holds dims/32 fragments: hd/32 for GQA (4 at hd=128,
+//     8 at hd=256), 18 for MLA
 //   V image of a head: [d>>4][pos>>5][lane][pos&7], lane = ((pos&31)>>3)*16 + (d&15)
-//     one fragment per (16-dim group, 32-position tile): 8 groups GQA, 32 MLA
-constexpr int FRAG = 512;            // elements per fragment
-constexpr int GQA_KTILE = 4 * FRAG;  // one 16-position K tile at hd = 128
-constexpr int GQA_VGROUPS = 8;       // 16-dim V groups at hd = 128
+//     one fragment per (16-dim group, 32-position tile): hd/16 groups GQA
+//     (8 at hd=128, 16 at hd=256), 32 MLA
+// The GQA kernels take the packed layouts at hd in {128, 256} (GQA_PACKED_HD).
+constexpr int FRAG = 512;  // elements per fragment
+constexpr bool GQA_PACKED_HD(int hd) { return hd == 128 || hd == 256; }
+constexpr int GQA_KTILE(int hd) { return (hd >> 5) * FRAG; }  // one 16-position K tile
+constexpr int GQA_VGROUPS(int hd) { return hd >> 4; }         // 16-dim V groups
 
 // offset of (dim d, position pos) inside its 16-position K tile
 DEVINL size_t kfrag_off(int d, int pos) {
@@ -199,12 +203,15 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(
 // cos/sin tables fp32 [maxT, hd/2].
 // ---------------------------------------------------------------------------
 
-// When the MFMA-packed cache copies exist (kpc/vpc non-null, hd == 128) the
-// same kernel also appends into them (decode attention then streams the
+// When the MFMA-packed cache copies exist (kpc/vpc non-null, hd 128 or 256)
+// the same kernel also appends into them (decode attention then streams the
 // cache as coalesced v_mfma_f32_16x16x32_bf16 B-fragments), per (b, kv-head)
 // in the kfrag_off / vfrag_off layouts:
-//   K_packed [B,KVH][T32/16 tile][4 hd-chunk][64 lane][8]
-//   V_packed [B,KVH][8 hd-group][T32/32 tile][64 lane][8]
+//   K_packed [B,KVH][T32/16 tile][hd/32 hd-chunk][64 lane][8]
+//   V_packed [B,KVH][hd/16 hd-group][T32/32 tile][64 lane][8]
+// A wave owns hd/2 rotate pairs: PAIRS = 1 per lane up to hd = 128, 2 at
+// hd <= 256 (pair e of a lane is dims p, p + hd/2 with p = lane + 64 e; the V
+// copy moves dims 128 e + 2 lane, + 1).
 // Optional qwen3 per-head q/k RMSNorm (qn/kn weights [hd], fused before the
 // rotation): the slot's wave reduces sum-of-squares over the head row, then
 // scales while rotating.
@@ -212,29 +219,48 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(
 // per-row scales sk/sv [B*KVH*T32] — half the decode stream and ~60% of the
 // dual-cache residency (plain cache stays bf16 for prefill). XOT_FP8_KV=1.
 
-// this lane's rotated pair (dims lane, lane + hd/2) of one q or k head row,
-// after the optional per-head RMSNorm (w non-null); lanes >= hd/2 get 0
+// this lane's rotated pairs (pair e: dims p, p + hd/2, p = lane + 64 e) of one
+// q or k head row, after the optional per-head RMSNorm (w non-null) over the
+// whole row; pairs with p >= hd/2 get 0
+template <int PAIRS>
 DEVINL void rope_head_pair(const unsigned short* row, const unsigned short* __restrict__ w,
                            const float* __restrict__ cosb, const float* __restrict__ sinb,
-                           int pos, int hd, int lane, float eps, float& f1, float& f2) {
+                           int pos, int hd, int lane, float eps, float (&f1)[PAIRS], float (&f2)[PAIRS]) {
   const int hd2 = hd >> 1;
-  const bool on = lane < hd2;
-  float x1 = 0.f, x2 = 0.f;
-  if (on) {
-    x1 = b2f(row[lane]);
-    x2 = b2f(row[lane + hd2]);
-  }
-  if (w) {
-    const float inv = rsqrtf(wave_sum(x1 * x1 + x2 * x2) / (float)hd + eps);
-    if (on) {
-      x1 *= inv * b2f(w[lane]);
-      x2 *= inv * b2f(w[lane + hd2]);
+  float x1[PAIRS], x2[PAIRS];
+#pragma unroll
+  for (int e = 0; e < PAIRS; ++e) {
+    const int p = lane + e * 64;
+    x1[e] = x2[e] = 0.f;
+    if (p < hd2) {
+      x1[e] = b2f(row[p]);
+      x2[e] = b2f(row[p + hd2]);
     }
   }
-  rope_pair(x1, x2, on ? cosb[(size_t)pos * hd2 + lane] : 0.f,
-            on ? sinb[(size_t)pos * hd2 + lane] : 0.f, f1, f2);
+  if (w) {
+    float ss = x1[0] * x1[0] + x2[0] * x2[0];
+#pragma unroll
+    for (int e = 1; e < PAIRS; ++e) ss += x1[e] * x1[e] + x2[e] * x2[e];
+    const float inv = rsqrtf(wave_sum(ss) / (float)hd + eps);
+#pragma unroll
+    for (int e = 0; e < PAIRS; ++e) {
+      const int p = lane + e * 64;
+      if (p < hd2) {
+        x1[e] *= inv * b2f(w[p]);
+        x2[e] *= inv * b2f(w[p + hd2]);
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < PAIRS; ++e) {
+    const int p = lane + e * 64;
+    const bool on = p < hd2;
+    rope_pair(x1[e], x2[e], on ? cosb[(size_t)pos * hd2 + p] : 0.f,
+              on ? sinb[(size_t)pos * hd2 + p] : 0.f, f1[e], f2[e]);
+  }
 }
 
+template <int PAIRS>
 __global__ __launch_bounds__(256) void rope_qkv_append_kernel(
     unsigned short* __restrict__ qkv, const float* __restrict__ cosb,
     const float* __restrict__ sinb, const int* __restrict__ positions,
@@ -256,56 +282,78 @@ __global__ __launch_bounds__(256) void rope_qkv_append_kernel(
   const int hd2 = hd >> 1;
   unsigned short* row = qkv + ((size_t)bs * slots + slot) * hd;
   if (slot < H) {
-    float f1, f2;
+    float f1[PAIRS], f2[PAIRS];
     rope_head_pair(row, qn, cosb, sinb, pos, hd, lane, norm_eps, f1, f2);
-    if (lane < hd2) {
-      row[lane] = f2b(f1);
-      row[lane + hd2] = f2b(f2);
+#pragma unroll
+    for (int e = 0; e < PAIRS; ++e) {
+      const int p = lane + e * 64;
+      if (p < hd2) {
+        row[p] = f2b(f1[e]);
+        row[p + hd2] = f2b(f2[e]);
+      }
     }
   } else if (slot < H + KVH) {
     const size_t head = (size_t)(b * KVH + (slot - H));
-    float f1, f2;
+    float f1[PAIRS], f2[PAIRS];
     rope_head_pair(row, kn, cosb, sinb, pos, hd, lane, norm_eps, f1, f2);
-    const size_t ktile = (head * (T32 >> 4) + (pos >> 4)) * GQA_KTILE;
-    const size_t o1 = ktile + kfrag_off(lane, pos), o2 = ktile + kfrag_off(lane + hd2, pos);
-    if (lane < hd2) {
-      unsigned short* dst = kc + (head * T + pos) * hd;
-      dst[lane] = f2b(f1);
-      dst[lane + hd2] = f2b(f2);
-      if (kpc) {
-        kpc[o1] = f2b(f1);
-        kpc[o2] = f2b(f2);
+    const size_t ktile = (head * (T32 >> 4) + (pos >> 4)) * GQA_KTILE(hd);
+    unsigned short* dst = kc + (head * T + pos) * hd;
+    float mx = 0.f;
+#pragma unroll
+    for (int e = 0; e < PAIRS; ++e) {
+      const int p = lane + e * 64;
+      mx = fmaxf(mx, fmaxf(fabsf(f1[e]), fabsf(f2[e])));
+      if (p < hd2) {
+        dst[p] = f2b(f1[e]);
+        dst[p + hd2] = f2b(f2[e]);
+        if (kpc) {
+          kpc[ktile + kfrag_off(p, pos)] = f2b(f1[e]);
+          kpc[ktile + kfrag_off(p + hd2, pos)] = f2b(f2[e]);
+        }
       }
     }
     if (kp8) {
-      const float scl = e4m3_scale(wave_max(fmaxf(fabsf(f1), fabsf(f2))));
+      const float scl = e4m3_scale(wave_max(mx));
       const float inv = 1.f / scl;
       if (lane == 0) sk[head * T32 + pos] = scl;
-      if (lane < hd2) {
-        kp8[o1] = to_e4m3(f1 * inv);
-        kp8[o2] = to_e4m3(f2 * inv);
+#pragma unroll
+      for (int e = 0; e < PAIRS; ++e) {
+        const int p = lane + e * 64;
+        if (p < hd2) {
+          kp8[ktile + kfrag_off(p, pos)] = to_e4m3(f1[e] * inv);
+          kp8[ktile + kfrag_off(p + hd2, pos)] = to_e4m3(f2[e] * inv);
+        }
       }
     }
   } else {
     const size_t head = (size_t)(b * KVH + (slot - H - KVH));
     unsigned short* dst = vc + (head * T + pos) * hd;
-    const bool on = lane * 2 < hd;
-    if (on) *(unsigned int*)(dst + lane * 2) = *(const unsigned int*)(row + lane * 2);
-    const size_t vhead = head * GQA_VGROUPS * (T32 >> 5) * FRAG;
-    if (vpc && on) {
+    const size_t vhead = head * GQA_VGROUPS(hd) * (T32 >> 5) * FRAG;
+    float mx = 0.f;
 #pragma unroll
-      for (int e = 0; e < 2; ++e) vpc[vhead + vfrag_off(lane * 2 + e, pos, T32 >> 5)] = row[lane * 2 + e];
+    for (int e = 0; e < PAIRS; ++e) {
+      const int d = e * 128 + lane * 2;
+      if (d < hd) {
+        *(unsigned int*)(dst + d) = *(const unsigned int*)(row + d);
+        mx = fmaxf(mx, fmaxf(fabsf(b2f(row[d])), fabsf(b2f(row[d + 1]))));
+        if (vpc) {
+#pragma unroll
+          for (int j = 0; j < 2; ++j) vpc[vhead + vfrag_off(d + j, pos, T32 >> 5)] = row[d + j];
+        }
+      }
     }
     if (vp8) {
-      float mx = 0.f;
-      if (on) mx = fmaxf(fabsf(b2f(row[lane * 2])), fabsf(b2f(row[lane * 2 + 1])));
       const float scl = e4m3_scale(wave_max(mx));
       const float inv = 1.f / scl;
       if (lane == 0) sv[head * T32 + pos] = scl;
-      if (on) {
 #pragma unroll
-        for (int e = 0; e < 2; ++e)
-          vp8[vhead + vfrag_off(lane * 2 + e, pos, T32 >> 5)] = to_e4m3(b2f(row[lane * 2 + e]) * inv);
+      for (int e = 0; e < PAIRS; ++e) {
+        const int d = e * 128 + lane * 2;
+        if (d < hd) {
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            vp8[vhead + vfrag_off(d + j, pos, T32 >> 5)] = to_e4m3(b2f(row[d + j]) * inv);
+        }
       }
     }
   }
@@ -324,7 +372,7 @@ __global__ __launch_bounds__(256) void rope_qkv_append_kernel(
 // ---------------------------------------------------------------------------
 
 // merge of the split-KV partials (VALU, MFMA and MLA decode): one workgroup
-// per (b, head), 128 threads (256 at HD = 512), HD / threads dims per thread
+// per (b, head), 128 threads (256 at HD 256 and 512), HD / threads dims per thread
 template <int HD>
 __global__ __launch_bounds__(HD > 128 ? 256 : 128) void attn_decode_merge(
     const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
@@ -471,20 +519,20 @@ __global__ __launch_bounds__(256) void attn_decode_partial(
 }
 
 // ---------------------------------------------------------------------------
-// MFMA flash-decoding attention (hd = 128): scores and PV on matrix cores.
+// MFMA flash-decoding attention (HD = 128 or 256): scores and PV on matrix cores.
 //
 // One WAVE per (b, kv-head, kv-split); the wave's all NQ (<=16) query heads
 // are scored together: per 32-position tile,
-//   scores[16q][32p] = 2 x (4 x v_mfma_f32_16x16x32_bf16)  (Q fragments resident,
+//   scores[16q][32p] = 2 x (HD/32 x v_mfma_f32_16x16x32_bf16)  (Q fragments resident,
 //                      K streamed from the packed cache as coalesced 1 KB loads)
 //   online softmax row stats via 4 shfl_xor over the 16-lane column groups
 //   P -> bf16 A-fragments through a 96 B-stride LDS image (conflict-free)
-//   out[16q][128] += 8 x v_mfma_f32_16x16x32_bf16 (V streamed packed)
+//   out[16q][HD] += HD/16 x v_mfma_f32_16x16x32_bf16 (V streamed packed)
 // No cross-wave barriers in the position loop (per-wave LDS slice), so ragged
 // per-batch lengths cannot deadlock. With nsplit <= 4 the workgroup merges its
 // own splits after one barrier that every wave reaches (attn_merge_in_workgroup);
 // otherwise partials go to the same (m, l, o) workspace as the VALU kernel and
-// are merged by attn_decode_merge<128>.
+// are merged by attn_decode_merge<HD> (256 threads x 1 dim at HD = 256).
 // Replaces the torchtune cached-decode step (reference general_mha.py:211-215);
 // the VALU split-KV kernel above stays as the hd=64 / unpacked-cache path.
 // ---------------------------------------------------------------------------
@@ -628,53 +676,62 @@ DEVINL void attn_store_partial(float* __restrict__ ws_o, float* __restrict__ ws_
 // (b, kv-head) groups of a workgroup hold every split of their rows, so the
 // waves exchange their partials through LDS and write final bf16 rows — no
 // workspace round trip, no merge launch. A wave's slab is 16 query rows of
-// ATTN_MROW floats: o[128], then m and l in the pad; 4 * 132 = 16 (mod 32)
-// keeps the four row groups of a store on distinct banks. The slab starts at
-// the wave's own P image, which is dead once its position loop has ended, so
-// the one barrier below is the only synchronisation needed.
+// ATTN_MROW(hd) = hd + 4 floats: o[hd], then m and l in the pad; 4 * 132 and
+// 4 * 260 = 16 (mod 32) keep the four row groups of a store on distinct
+// banks. The slab starts at the wave's own P image, which is dead once its
+// position loop has ended, so the one barrier below is the only
+// synchronisation needed.
 // The arithmetic and the split order are attn_decode_merge's, term for term:
 // the result is bit-identical to the workspace path.
-constexpr int ATTN_MROW = 132;
-constexpr int ATTN_MSLAB = 16 * ATTN_MROW;
+constexpr int ATTN_MROW(int hd) { return hd + 4; }
+constexpr int ATTN_MSLAB(int hd) { return 16 * ATTN_MROW(hd); }
 
 template <int NG>
 DEVINL void attn_merge_in_workgroup(float* __restrict__ lds, unsigned short* __restrict__ out,
                                     const floatx4 (&acco)[NG], const float (&m)[4], const float (&lsum)[4],
                                     int wv, int lane, int nq, int bh0, int nsplit, float oscale, bool live) {
-  static_assert(NG * 16 == 128, "merge slab rows hold 128 dims");
+  constexpr int HD = NG * 16, MROW = ATTN_MROW(HD), MSLAB = ATTN_MSLAB(HD);
+  static_assert(GQA_PACKED_HD(HD), "merge slab rows hold 128 or 256 dims");
   const int col = lane & 15;
-  float* mine = lds + wv * ATTN_MSLAB;
+  float* mine = lds + wv * MSLAB;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int qrow = (lane >> 4) * 4 + r;
     if (live && qrow < nq) {
 #pragma unroll
-      for (int g = 0; g < NG; ++g) mine[qrow * ATTN_MROW + g * 16 + col] = acco[g][r] * oscale;
+      for (int g = 0; g < NG; ++g) mine[qrow * MROW + g * 16 + col] = acco[g][r] * oscale;
       if (col == 0) {
-        mine[qrow * ATTN_MROW + 128] = m[r];
-        mine[qrow * ATTN_MROW + 129] = lsum[r];
+        mine[qrow * MROW + HD] = m[r];
+        mine[qrow * MROW + HD + 1] = lsum[r];
       }
     }
   }
   __syncthreads();
   if (!live) return;
-  // the group's nsplit waves share its nq rows; a lane owns dims 2*lane, 2*lane+1
+  // the group's nsplit waves share its nq rows; a lane owns dims 2*lane,
+  // 2*lane+1 of every 128-dim half
   const int split = wv % nsplit;
-  const float* grp = lds + (wv - split) * ATTN_MSLAB;
+  const float* grp = lds + (wv - split) * MSLAB;
   for (int row = split; row < nq; row += nsplit) {
-    const float* rp = grp + row * ATTN_MROW;
+    const float* rp = grp + row * MROW;
     float M = -INFINITY;
-    for (int i = 0; i < nsplit; ++i) M = fmaxf(M, rp[i * ATTN_MSLAB + 128]);
-    float L = 0.f, O0 = 0.f, O1 = 0.f;
+    for (int i = 0; i < nsplit; ++i) M = fmaxf(M, rp[i * MSLAB + HD]);
+    float L = 0.f, O0[HD / 128] = {}, O1[HD / 128] = {};
     for (int i = 0; i < nsplit; ++i) {
-      const float lg = rp[i * ATTN_MSLAB + 129];
-      const float alpha = (lg > 0.f) ? __expf(rp[i * ATTN_MSLAB + 128] - M) : 0.f;
+      const float lg = rp[i * MSLAB + HD + 1];
+      const float alpha = (lg > 0.f) ? __expf(rp[i * MSLAB + HD] - M) : 0.f;
       L += alpha * lg;
-      O0 += alpha * rp[i * ATTN_MSLAB + lane * 2];
-      O1 += alpha * rp[i * ATTN_MSLAB + lane * 2 + 1];
+#pragma unroll
+      for (int e = 0; e < HD / 128; ++e) {
+        O0[e] += alpha * rp[i * MSLAB + e * 128 + lane * 2];
+        O1[e] += alpha * rp[i * MSLAB + e * 128 + lane * 2 + 1];
+      }
     }
-    const unsigned int lo = f2b(L > 0.f ? O0 / L : 0.f), hi = f2b(L > 0.f ? O1 / L : 0.f);
-    *reinterpret_cast<unsigned int*>(out + (size_t)(bh0 + row) * 128 + lane * 2) = lo | (hi << 16);
+#pragma unroll
+    for (int e = 0; e < HD / 128; ++e) {
+      const unsigned int lo = f2b(L > 0.f ? O0[e] / L : 0.f), hi = f2b(L > 0.f ? O1[e] / L : 0.f);
+      *reinterpret_cast<unsigned int*>(out + (size_t)(bh0 + row) * HD + e * 128 + lane * 2) = lo | (hi << 16);
+    }
   }
 }
 
@@ -689,8 +746,11 @@ DEVINL void attn_merge_in_workgroup(float* __restrict__ lds, unsigned short* __r
 // 3 waves/SIMD is what the position loop reaches on its own (136 VGPR + 32
 // AGPR with PREFETCH); stated, because with the merge slabs in LDS the
 // register allocator otherwise spends a wave of occupancy (168 + 32).
-template <bool PREFETCH = false, bool FP8 = false>
-__global__ __launch_bounds__(256, 3) void attn_decode_mfma_kernel(
+// HD = 256 doubles acco (64 registers) and kbuf (64 with PREFETCH): the bf16
+// PREFETCH variant takes all 256 VGPRs of 2 waves/SIMD without scratch, and
+// only two 65 KB workgroups fit a CU's 160 KB LDS, so 2 is stated there.
+template <bool PREFETCH = false, bool FP8 = false, int HD = 128>
+__global__ __launch_bounds__(256, HD > 128 ? 2 : 3) void attn_decode_mfma_kernel(
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ kp,
     const unsigned short* __restrict__ vp, const int* __restrict__ seq_lens,
     float* __restrict__ ws_o, float* __restrict__ ws_ml,
@@ -698,13 +758,15 @@ __global__ __launch_bounds__(256, 3) void attn_decode_mfma_kernel(
     float softcap, int window,
     const float* __restrict__ sk = nullptr, const float* __restrict__ sv = nullptr,
     unsigned short* __restrict__ out = nullptr) {
+  static_assert(GQA_PACKED_HD(HD), "packed GQA cache: head_dim 128 or 256");
+  constexpr int NC = HD / 32, NG = GQA_VGROUPS(HD), KTILE = GQA_KTILE(HD);  // qk chunks, pv groups
   const int wv = threadIdx.x >> 6;
   const int wid = blockIdx.x * 4 + wv;
   // The kernel's one LDS object: each wave's merge slab, whose head doubles as
   // its P image (16 rows, 96 B row stride: bank-conflict-free b128 reads).
   // Declared in the P image's element type: declared as float and cast for
   // the loop, the same kernel measured 60 us instead of 48 at B=128, sl=540.
-  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][ATTN_MSLAB * 2];
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][ATTN_MSLAB(HD) * 2];
   // out != null selects the in-workgroup merge: waves past the end (whole
   // groups, as nsplit divides 4) then stay for its barrier with an empty
   // position range and touch no global memory.
@@ -730,20 +792,20 @@ __global__ __launch_bounds__(256, 3) void attn_decode_mfma_kernel(
   // Q fragments: A[i = lane&15 (query head, clamped), k = (lane>>4)*8 + j]
   const int qh_base = kvh * NQ;
   const int qi = min(lane & 15, NQ - 1);
-  FT qf[4];
+  FT qf[NC];
   float srow[4];
   {
-    const unsigned short* qrow = q + (size_t)b * q_stride + (size_t)(qh_base + qi) * 128 + (lane >> 4) * 8;
-    bf16x8 qb[4] = {};
+    const unsigned short* qrow = q + (size_t)b * q_stride + (size_t)(qh_base + qi) * HD + (lane >> 4) * 8;
+    bf16x8 qb[NC] = {};
     if (live) {
 #pragma unroll
-      for (int c = 0; c < 4; ++c) qb[c] = frag_load<false>(qrow + c * 32);
+      for (int c = 0; c < NC; ++c) qb[c] = frag_load<false>(qrow + c * 32);
     }
     if constexpr (FP8) {
-      // quantize per head: amax over the 4 lanes x 32 elements of the row
+      // quantize per head: amax over the 4 lanes x HD / 4 elements of the row
       float mx = 0.f;
 #pragma unroll
-      for (int c = 0; c < 4; ++c)
+      for (int c = 0; c < NC; ++c)
 #pragma unroll
         for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf((float)qb[c][j]));
       mx = fmaxf(mx, __shfl_xor(mx, 16));
@@ -751,42 +813,42 @@ __global__ __launch_bounds__(256, 3) void attn_decode_mfma_kernel(
       const float sq = e4m3_scale(mx);
       const float inv = 1.f / sq;
 #pragma unroll
-      for (int c = 0; c < 4; ++c) qf[c] = to_e4m3x8(qb[c], inv);
+      for (int c = 0; c < NC; ++c) qf[c] = to_e4m3x8(qb[c], inv);
 #pragma unroll
       for (int r = 0; r < 4; ++r) srow[r] = __shfl(sq, (lane >> 4) * 4 + r);
     } else {
 #pragma unroll
-      for (int c = 0; c < 4; ++c) qf[c] = qb[c];
+      for (int c = 0; c < NC; ++c) qf[c] = qb[c];
     }
   }
 
   float m[4], lsum[4], Rscale = 1.f;
-  floatx4 acco[GQA_VGROUPS];
+  floatx4 acco[NG];
 #pragma unroll
   for (int r = 0; r < 4; ++r) { m[r] = -INFINITY; lsum[r] = 0.f; }
 #pragma unroll
-  for (int g = 0; g < GQA_VGROUPS; ++g) acco[g] = (floatx4)(0.f);
+  for (int g = 0; g < NG; ++g) acco[g] = (floatx4)(0.f);
 
   // this (b, kv-head)'s K / V images at this lane's slice of every fragment,
   // and (fp8) its per-position scale rows
   const size_t head = (size_t)(b * KVH + kvh);
-  const FE* khead = reinterpret_cast<const FE*>(kp) + head * (T32 >> 4) * GQA_KTILE + lane * 8;
-  const FE* vhead = reinterpret_cast<const FE*>(vp) + head * GQA_VGROUPS * (T32 >> 5) * FRAG + lane * 8;
+  const FE* khead = reinterpret_cast<const FE*>(kp) + head * (T32 >> 4) * KTILE + lane * 8;
+  const FE* vhead = reinterpret_cast<const FE*>(vp) + head * NG * (T32 >> 5) * FRAG + lane * 8;
   const float* ks_row = FP8 ? sk + head * T32 : nullptr;
   const float* vs_row = FP8 ? sv + head * T32 : nullptr;
   const int col = lane & 15;
 
-  // the 8 K fragments (2 half-tiles x 4 hd-chunks) of the 32-position tile at t.
+  // the 2 * NC K fragments (2 half-tiles x NC hd-chunks) of the 32-position tile at t.
   // PREFETCH: the next tile's are loaded during the previous tile's PV phase
-  // (kbuf stays live, +32 VGPR) so the score MFMAs never wait on HBM;
+  // (kbuf stays live, +32 VGPR at hd 128, +64 at 256) so the score MFMAs never wait on HBM;
   // measured A/B via XOT_ATTN_PREFETCH.
-  FT kbuf[8];
+  FT kbuf[2 * NC];
   auto load_k_tile = [&](int t) {
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
-      for (int c = 0; c < 4; ++c)
-        kbuf[h * 4 + c] = frag_load_nt<FP8>(khead + (size_t)((t >> 4) + h) * GQA_KTILE + c * FRAG);
+      for (int c = 0; c < NC; ++c)
+        kbuf[h * NC + c] = frag_load_nt<FP8>(khead + (size_t)((t >> 4) + h) * KTILE + c * FRAG);
   };
   if (PREFETCH && c0 < c1) load_k_tile(c0);
 
@@ -798,7 +860,7 @@ __global__ __launch_bounds__(256, 3) void attn_decode_mfma_kernel(
     for (int h = 0; h < 2; ++h) {
       sc[h] = (floatx4)(0.f);
 #pragma unroll
-      for (int c = 0; c < 4; ++c) sc[h] = F::mfma(qf[c], kbuf[h * 4 + c], sc[h]);
+      for (int c = 0; c < NC; ++c) sc[h] = F::mfma(qf[c], kbuf[h * NC + c], sc[h]);
     }
     // ---- scale, softcap, mask (rows r are this lane's 4 query heads) ----
 #pragma unroll
@@ -824,11 +886,11 @@ __global__ __launch_bounds__(256, 3) void attn_decode_mfma_kernel(
     // ---- PV: out[16q][g*16..] += P x V ----
     const FE* vt = vhead + (size_t)(t >> 5) * FRAG;
 #pragma unroll
-    for (int g = 0; g < GQA_VGROUPS; ++g)
+    for (int g = 0; g < NG; ++g)
       acco[g] = F::mfma(pf, frag_load_nt<FP8>(vt + (size_t)g * (T32 >> 5) * FRAG), acco[g]);
   }
 
-  // ---- epilogue: final rows merged in the workgroup, or one (m, l, o[128])
+  // ---- epilogue: final rows merged in the workgroup, or one (m, l, o[HD])
   // partial per (b, qh, split) for attn_decode_merge ----
   if (out != nullptr)
     attn_merge_in_workgroup(reinterpret_cast<float*>(&plds_all[0][0]), out, acco, m, lsum, wv, lane, NQ, b * H + qh_base, nsplit,
@@ -839,7 +901,7 @@ __global__ __launch_bounds__(256, 3) void attn_decode_mfma_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// MFMA flash-forward prefill attention (hd = 128, causal, GQA).
+// MFMA flash-forward prefill attention (HD = 128 or 256, causal, GQA).
 //
 // Replaces torch sdpa for the prefill step (reference: torchtune
 // MultiHeadAttention prefill, general_mha.py:218-226; sdpa measures ~1.8 ms
@@ -847,19 +909,31 @@ __global__ __launch_bounds__(256, 3) void attn_decode_mfma_kernel(
 // workgroup per (b, q-head, 128-row q block); the block's waves share K/V
 // tiles staged in LDS from the MFMA-packed cache (fragment layout is
 // lane-linear, so staging is 1 KB coalesced loads and conflict-free b128
-// reads).  Each wave owns 32 q rows (2 MFMA sub-tiles), walks kv position
+// reads).  Each wave owns 32 q rows (2 MFMA sub-tiles; 16 rows and 64-row q
+// blocks at HD = 256, ATTN_PREFILL_NT), walks kv position
 // tiles of 32 with online softmax, masks the causal boundary, writes final
 // bf16 rows (no split-K workspace).
 // ---------------------------------------------------------------------------
 
+// 16-row MFMA sub-tiles per wave (NT): 2 at HD = 128 (128-row q blocks). At
+// HD = 256 two sub-tiles still compile without scratch (256 VGPR + 156 AGPR)
+// but leave 1 wave/SIMD; one sub-tile (64-row q blocks) runs 2 waves/SIMD and
+// measured 0.56 ms against 1.43 ms for a B=64 x S=512, H=16 layer.
+constexpr int ATTN_PREFILL_NT(int hd) { return hd > 128 ? 1 : 2; }
+
+template <int HD, int NT>
 __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ kp,
     const unsigned short* __restrict__ vp, unsigned short* __restrict__ out,
     int B, int S, int H, int KVH, int T32, int start_pos,
     long long q_bstride, long long q_sstride, float scale,
     float softcap, int window) {
+  static_assert(GQA_PACKED_HD(HD), "packed GQA cache: head_dim 128 or 256");
+  constexpr int NC = HD / 32, NG = GQA_VGROUPS(HD), KTILE = GQA_KTILE(HD);  // qk chunks, pv groups
+  static_assert(NT == 1 || NT == 2, "a wave owns one or two 16-row sub-tiles");
+  constexpr int QSHIFT = NT == 2 ? 7 : 6, QROWS = 1 << QSHIFT;  // q rows per block: 4 waves x NT x 16
   // block -> (b, h, q-block)
-  const int qblocks = (S + 127) >> 7;
+  const int qblocks = (S + QROWS - 1) >> QSHIFT;
   const int h = blockIdx.x % H;
   const int t1 = blockIdx.x / H;
   const int qb = t1 % qblocks;
@@ -868,63 +942,62 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
   const int lane = threadIdx.x & 63;
   const int kvh = h / (H / KVH);
 
-  // this wave's 32 q rows: [r0, r0+32)
-  const int r0 = qb * 128 + wv * 32;
+  // this wave's 16 * NT q rows: [r0, r0 + 16 * NT)
+  const int r0 = qb * QROWS + wv * (16 * NT);
   const int col = lane & 15;
 
-  constexpr int KV_K = 2 * GQA_KTILE, KV_V = GQA_VGROUPS * FRAG;
+  constexpr int KV_K = 2 * KTILE, KV_V = NG * FRAG;
   __shared__ unsigned short kv_lds[2][KV_K + KV_V];  // dbuf
 
-  // Q fragments for 2 sub-tiles x 4 hd-chunks; rows clamped to S-1 (writes
+  // Q fragments for NT sub-tiles x NC hd-chunks; rows clamped to S-1 (writes
   // are predicated, extra rows only waste compute)
-  bf16x8 qf[2][4];
+  bf16x8 qf[NT][NC];
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
+  for (int t = 0; t < NT; ++t) {
     const int row = min(r0 + t * 16 + col, S - 1);
-    const unsigned short* qrow = q + (size_t)b * q_bstride + (size_t)row * q_sstride + (size_t)h * 128;
+    const unsigned short* qrow = q + (size_t)b * q_bstride + (size_t)row * q_sstride + (size_t)h * HD;
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
+    for (int c = 0; c < NC; ++c)
       qf[t][c] = frag_load<false>(qrow + c * 32 + (lane >> 4) * 8);
   }
 
-  float m[2][4], lsum[2][4];
-  floatx4 acco[2][GQA_VGROUPS];
+  float m[NT][4], lsum[NT][4];
+  floatx4 acco[NT][NG];
 #pragma unroll
-  for (int t = 0; t < 2; ++t)
+  for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) { m[t][r] = -INFINITY; lsum[t][r] = 0.f; }
 #pragma unroll
-  for (int t = 0; t < 2; ++t)
+  for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int g = 0; g < 8; ++g) acco[t][g] = (floatx4)(0.f);
+    for (int g = 0; g < NG; ++g) acco[t][g] = (floatx4)(0.f);
 
-  const size_t kbase = (size_t)(b * KVH + kvh) * (T32 >> 4) * GQA_KTILE;
-  const size_t vbase = (size_t)(b * KVH + kvh) * GQA_VGROUPS * (T32 >> 5) * FRAG;
+  const size_t kbase = (size_t)(b * KVH + kvh) * (T32 >> 4) * KTILE;
+  const size_t vbase = (size_t)(b * KVH + kvh) * NG * (T32 >> 5) * FRAG;
   // causal end for the BLOCK (max row): positions [0, start_pos + block_hi]
-  const int block_hi = min(qb * 128 + 127, S - 1);
+  const int block_hi = min(qb * QROWS + QROWS - 1, S - 1);
   const int kv_end = start_pos + block_hi + 1;  // exclusive
 
-  __shared__ unsigned short plds_all[4][16 * 48 * 2];
+  __shared__ unsigned short plds_all[4][16 * 48 * NT];
 
   // cooperative stage of kv tile `tp` (32 positions) into kv_lds[buf]
   auto stage = [&](int tp, int buf) {
-    // K: two 16-pos tiles x 4 chunks x 512 elems; V: 8 groups x 512 elems
-    // 256 threads x 24 pieces of 256 B... simpler: each thread copies 16 B x3
-    const unsigned short* ksrc = kp + kbase + (size_t)(tp * 2) * GQA_KTILE;
+    // K: two 16-pos tiles x NC chunks x 512 elems; V: NG groups x 512 elems
+    const unsigned short* ksrc = kp + kbase + (size_t)(tp * 2) * KTILE;
     const unsigned short* vsrc = vp + vbase + (size_t)tp * FRAG;
     unsigned short* dk = kv_lds[buf];
     unsigned short* dv = kv_lds[buf] + KV_K;
     const int tid = threadIdx.x;
-    // K: 4096 elems = 8192 B: 256 threads x 2 x 16 B
+    // K: KV_K elems (8 KB at hd 128, 16 KB at 256): 256 threads x KV_K / 2048 x 16 B
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < KV_K / 2048; ++i) {
       const int e = (tid + i * 256) * 8;
       *(ushort8*)(dk + e) = *(const ushort8*)(ksrc + e);
     }
-    // V: 8 groups x 512 elems, group stride (T32>>5)*512 in global
+    // V: NG groups x 512 elems, group stride (T32>>5)*512 in global
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int e = tid + i * 256;           // 0..511 -> (group, piece)
+    for (int i = 0; i < NG / 4; ++i) {
+      const int e = tid + i * 256;           // 0..NG*64-1 -> (group, piece)
       const int g = e >> 6, piece = e & 63;  // 64 pieces of 8 elems per group
       *(ushort8*)(dv + g * FRAG + piece * 8) =
           *(const ushort8*)(vsrc + (size_t)g * (T32 >> 5) * FRAG + piece * 8);
@@ -933,8 +1006,8 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
 
   const int ntiles = (kv_end + 31) >> 5;
   // sliding window: the block's lowest q row sees nothing before
-  // start_pos + qb*128 - window + 1 — skip whole kv tiles below it
-  const int tp0 = (window > 0) ? max(0, (start_pos + qb * 128 - window + 1) >> 5) : 0;
+  // start_pos + qb*QROWS - window + 1 — skip whole kv tiles below it
+  const int tp0 = (window > 0) ? max(0, (start_pos + qb * QROWS - window + 1) >> 5) : 0;
   stage(tp0, tp0 & 1);
   __syncthreads();
 
@@ -945,15 +1018,15 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
     const unsigned short* dv = kv_lds[buf] + KV_K;
     unsigned short* plds = plds_all[wv];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
+    for (int t = 0; t < NT; ++t) {
       // scores for two 16-pos halves of this kv tile
       floatx4 sc[2];
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
         sc[hh] = (floatx4)(0.f);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const bf16x8 kb = *reinterpret_cast<const bf16x8*>(dk + (hh * 4 + c) * FRAG + lane * 8);
+        for (int c = 0; c < NC; ++c) {
+          const bf16x8 kb = *reinterpret_cast<const bf16x8*>(dk + (hh * NC + c) * FRAG + lane * 8);
           sc[hh] = Frag<false>::mfma(qf[t][c], kb, sc[hh]);
         }
       }
@@ -998,7 +1071,7 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) lsum[t][r] = lsum[t][r] * alpha[r] + rsum[r];
       attn_rescale(acco[t], alpha, 1.f);
-      unsigned short* pl = plds + t * 16 * 48;  // reuse the 2x buffer per sub-tile
+      unsigned short* pl = plds + t * 16 * 48;  // one P image per sub-tile
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
@@ -1006,7 +1079,7 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
           pl[((lane >> 4) * 4 + r) * 48 + hh * 16 + col] = f2b(sc[hh][r]);
       const bf16x8 pf = *reinterpret_cast<const bf16x8*>(pl + (lane & 15) * 48 + (lane >> 4) * 8);
 #pragma unroll
-      for (int g = 0; g < 8; ++g) {
+      for (int g = 0; g < NG; ++g) {
         const bf16x8 vb = *reinterpret_cast<const bf16x8*>(dv + g * FRAG + lane * 8);
         acco[t][g] = Frag<false>::mfma(pf, vb, acco[t][g]);
       }
@@ -1016,15 +1089,15 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(
 
   // epilogue: out[b, row, h, g*16 + col] = acc / lsum
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
+  for (int t = 0; t < NT; ++t) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = r0 + t * 16 + (lane >> 4) * 4 + r;
       if (row < S) {
         const float inv = (lsum[t][r] > 0.f) ? 1.f / lsum[t][r] : 0.f;
-        unsigned short* orow = out + (((size_t)b * S + row) * H + h) * 128;
+        unsigned short* orow = out + (((size_t)b * S + row) * H + h) * HD;
 #pragma unroll
-        for (int g = 0; g < 8; ++g) orow[g * 16 + col] = f2b(acco[t][g][r] * inv);
+        for (int g = 0; g < NG; ++g) orow[g * 16 + col] = f2b(acco[t][g][r] * inv);
       }
     }
   }
@@ -2381,6 +2454,24 @@ static void dispatch_bool(bool v, F&& f) {
   if (v) f(std::true_type{}); else f(std::false_type{});
 }
 
+// head dim of the fragment-packed GQA cache -> IntC<128> / IntC<256>
+template <typename F>
+static void dispatch_packed_hd(int hd, const char* what, F&& f) {
+  switch (hd) {
+    case 128: f(IntC<128>{}); break;
+    case 256: f(IntC<256>{}); break;
+    default: TORCH_CHECK(false, what, ": head_dim must be 128 or 256, got ", hd);
+  }
+}
+
+// kp [B, KVH, T32/16, hd/32, 64, 8] and vp [B, KVH, hd/16, T32/32, 64, 8] of one head dim
+static void check_packed_gqa_shapes(const char* what, const torch::Tensor& kp, const torch::Tensor& vp, int hd) {
+  TORCH_CHECK(kp.dim() == 6 && vp.dim() == 6 && kp.size(3) == hd / 32 && vp.size(2) == hd / 16
+              && vp.size(3) * 2 == kp.size(2),
+              what, ": packed cache copies do not match head_dim ", hd,
+              " (accepted head dims: 128, 256; kp [B, KVH, T32/16, hd/32, 64, 8], vp [B, KVH, hd/16, T32/32, 64, 8])");
+}
+
 // packed-cache arguments of the append kernels: bf16 copies, or e4m3 copies
 // (uint8 tensors), which come with fp32 scale tensors
 struct PackedCachePtrs {
@@ -2462,7 +2553,7 @@ void rope_qkv_append(torch::Tensor qkv, torch::Tensor cos, torch::Tensor sin,
   const int H = (int)n_heads, KVH = (int)n_kv_heads, hd = (int)head_dim;
   const int T = kc.size(2);
   CHK(qkv.size(2) == (H + 2 * KVH) * hd);
-  CHK(hd <= 128 && hd % 2 == 0);
+  CHK(hd <= 256 && hd % 2 == 0);
   const int npos = (int)positions.numel();
   CHK(npos == S || npos == B * S);
   CHK(positions.is_contiguous());
@@ -2471,7 +2562,8 @@ void rope_qkv_append(torch::Tensor qkv, torch::Tensor cos, torch::Tensor sin,
   float* svp = nullptr;
   int T32 = 0;
   if (kp.has_value() && vp.has_value()) {
-    CHK(hd == 128);
+    TORCH_CHECK(GQA_PACKED_HD(hd), "rope_qkv_append: packed cache copies need head_dim 128 or 256, got ", hd);
+    check_packed_gqa_shapes("rope_qkv_append", *kp, *vp, hd);
     T32 = (int)kp->size(2) * 16;
     pc = packed_cache_ptrs(*kp, *vp);
     if (pc.kp8) {
@@ -2491,11 +2583,15 @@ void rope_qkv_append(torch::Tensor qkv, torch::Tensor cos, torch::Tensor sin,
   }
   const int waves = B * S * (H + 2 * KVH);
   const int blocks = (waves + 3) / 4;
-  hipLaunchKernelGGL(rope_qkv_append_kernel, dim3(blocks), dim3(256), 0, cur_stream(),
-                     (unsigned short*)qkv.data_ptr(), cos.data_ptr<float>(), sin.data_ptr<float>(),
-                     positions.data_ptr<int>(), (unsigned short*)kc.data_ptr(),
-                     (unsigned short*)vc.data_ptr(), B, S, H, KVH, hd, T, pc.kp, pc.vp, T32,
-                     qnp, knp, (float)norm_eps, npos, pc.kp8, pc.vp8, skp, svp);
+  // rotate pairs per lane: 1 up to hd = 128, 2 up to 256
+  dispatch_bool(hd > 128, [&](auto wide) {
+    hipLaunchKernelGGL((rope_qkv_append_kernel<decltype(wide)::value ? 2 : 1>), dim3(blocks), dim3(256), 0,
+                       cur_stream(),
+                       (unsigned short*)qkv.data_ptr(), cos.data_ptr<float>(), sin.data_ptr<float>(),
+                       positions.data_ptr<int>(), (unsigned short*)kc.data_ptr(),
+                       (unsigned short*)vc.data_ptr(), B, S, H, KVH, hd, T, pc.kp, pc.vp, T32,
+                       qnp, knp, (float)norm_eps, npos, pc.kp8, pc.vp8, skp, svp);
+  });
 }
 
 // Split-KV decode scaffolding shared by attn_decode, attn_decode_mfma and
@@ -2527,6 +2623,7 @@ struct SplitKV {
     switch (hd) {
       case 64: launch(IntC<64>{}); break;
       case 128: launch(IntC<128>{}); break;
+      case 256: launch(IntC<256>{}); break;
       case MLA_LAT: launch(IntC<MLA_LAT>{}); break;
       default: TORCH_CHECK(false, "split-KV merge: unsupported head dim ", hd);
     }
@@ -2566,7 +2663,7 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, t
   return kv.merge(stream);
 }
 
-// q: [B, 1, H, 128] (strided batch OK); kp/vp: the packed cache copies.
+// q: [B, 1, H, hd], hd 128 or 256 (strided batch OK); kp/vp: the packed cache copies.
 torch::Tensor attn_decode_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor vp,
                                torch::Tensor seq_lens, int64_t t_capacity,
                                double scale_in, double softcap, int64_t window,
@@ -2585,7 +2682,8 @@ torch::Tensor attn_decode_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor 
     svp = v_scale->data_ptr<float>();
   }
   const int B = q.size(0), H = q.size(2), hd = q.size(3);
-  TORCH_CHECK(hd == 128, "attn_decode_mfma requires head_dim 128");
+  TORCH_CHECK(GQA_PACKED_HD(hd), "attn_decode_mfma: head_dim must be 128 or 256, got ", hd);
+  check_packed_gqa_shapes("attn_decode_mfma", kp, vp, hd);
   const int KVH = kp.size(1);
   const int T32 = kp.size(2) * 16;
   const long long q_stride = q.stride(0);
@@ -2608,19 +2706,21 @@ torch::Tensor attn_decode_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor 
   const bool prefetch = (pf_env == nullptr) || (pf_env[0] != '0');
   dispatch_bool(prefetch, [&](auto pf) {
     dispatch_bool(fp8, [&](auto f8) {
-      hipLaunchKernelGGL((attn_decode_mfma_kernel<decltype(pf)::value, decltype(f8)::value>),
-                         dim3((waves + 3) / 4), dim3(256), 0, stream,
-                         (const unsigned short*)q.data_ptr(), (const unsigned short*)kp.data_ptr(),
-                         (const unsigned short*)vp.data_ptr(), seq_lens.data_ptr<int>(),
-                         kv.o(), kv.ml(), B, H, KVH, T32, nsplit, scale, q_stride,
-                         (float)softcap, (int)window, skp, svp,
-                         fused ? (unsigned short*)kv.out.data_ptr() : nullptr);
+      dispatch_packed_hd(hd, "attn_decode_mfma", [&](auto hdc) {
+        hipLaunchKernelGGL((attn_decode_mfma_kernel<decltype(pf)::value, decltype(f8)::value, decltype(hdc)::value>),
+                           dim3((waves + 3) / 4), dim3(256), 0, stream,
+                           (const unsigned short*)q.data_ptr(), (const unsigned short*)kp.data_ptr(),
+                           (const unsigned short*)vp.data_ptr(), seq_lens.data_ptr<int>(),
+                           kv.o(), kv.ml(), B, H, KVH, T32, nsplit, scale, q_stride,
+                           (float)softcap, (int)window, skp, svp,
+                           fused ? (unsigned short*)kv.out.data_ptr() : nullptr);
+      });
     });
   });
   return fused ? kv.out : kv.merge(stream);
 }
 
-// q: [B, S, H, 128] (strided over b/s OK, head rows contiguous); kp/vp: the
+// q: [B, S, H, hd], hd 128 or 256 (strided over b/s OK, head rows contiguous); kp/vp: the
 // packed cache copies already holding positions [0, start_pos + S).
 torch::Tensor attn_prefill_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor vp,
                                 int64_t start_pos, double scale_in, double softcap,
@@ -2629,19 +2729,24 @@ torch::Tensor attn_prefill_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor
   CHK(q.stride(3) == 1 && q.stride(2) == q.size(3));
   CHK(kp.is_contiguous() && vp.is_contiguous());
   const int B = q.size(0), S = q.size(1), H = q.size(2), hd = q.size(3);
-  TORCH_CHECK(hd == 128, "attn_prefill_mfma requires head_dim 128");
+  TORCH_CHECK(GQA_PACKED_HD(hd), "attn_prefill_mfma: head_dim must be 128 or 256, got ", hd);
+  TORCH_CHECK(kp.dtype() == torch::kBFloat16, "attn_prefill_mfma: bf16 packed cache copies only");
+  check_packed_gqa_shapes("attn_prefill_mfma", kp, vp, hd);
   const int KVH = kp.size(1);
   const int T32 = kp.size(2) * 16;
   CHK(start_pos + S <= T32);
   auto out = torch::empty({B, S, H, hd},
                           torch::TensorOptions().dtype(torch::kBFloat16).device(q.device()));
   const float scale = (scale_in > 0.0) ? (float)scale_in : 1.0f / sqrtf((float)hd);
-  const int qblocks = (S + 127) / 128;
-  hipLaunchKernelGGL(attn_prefill_mfma_kernel, dim3(B * qblocks * H), dim3(256), 0, cur_stream(),
-                     (const unsigned short*)q.data_ptr(), (const unsigned short*)kp.data_ptr(),
-                     (const unsigned short*)vp.data_ptr(), (unsigned short*)out.data_ptr(),
-                     B, S, H, KVH, T32, (int)start_pos, q.stride(0), q.stride(1), scale,
-                     (float)softcap, (int)window);
+  dispatch_packed_hd(hd, "attn_prefill_mfma", [&](auto hdc) {
+    constexpr int HD = decltype(hdc)::value, NT = ATTN_PREFILL_NT(HD);
+    const int qblocks = (S + 64 * NT - 1) / (64 * NT);
+    hipLaunchKernelGGL((attn_prefill_mfma_kernel<HD, NT>), dim3(B * qblocks * H), dim3(256), 0, cur_stream(),
+                       (const unsigned short*)q.data_ptr(), (const unsigned short*)kp.data_ptr(),
+                       (const unsigned short*)vp.data_ptr(), (unsigned short*)out.data_ptr(),
+                       B, S, H, KVH, T32, (int)start_pos, q.stride(0), q.stride(1), scale,
+                       (float)softcap, (int)window);
+  });
   return out;
 }
 
