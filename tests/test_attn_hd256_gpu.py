@@ -6,6 +6,8 @@ ones the same kernels are held to at head_dim 128."""
 import pytest
 import torch
 
+import attn_oracle as ao
+
 pytestmark = pytest.mark.gpu
 
 HD = 256
@@ -24,40 +26,8 @@ def rnd(*shape, scale=1.0, seed=0):
   return (torch.randn(*shape, generator=g, device="cuda", dtype=torch.float32) * scale).to(torch.bfloat16)
 
 
-# Reference packers for the two fragment layouts at a general head dim, stated
-# independently of the kernel:
-#   K: hd = c*32 + qt*8 + j, pos = tile*16 + p16, lane = qt*16 + p16
-#      -> [B, KVH, t32/16, hd/32, 64, 8]
-#   V: pos = tp*32 + qt*8 + j, hd = g*16 + c16, lane = qt*16 + c16
-#      -> [B, KVH, hd/16, t32/32, 64, 8]
-
-def _pad_t(x, t32):
-  B, KVH, T, hd = x.shape
-  out = torch.zeros(B, KVH, t32, hd, dtype=x.dtype, device=x.device)
-  out[:, :, :T] = x
-  return out
-
-
-def _pack_k(k, t32):
-  B, KVH, _, hd = k.shape
-  v = _pad_t(k, t32).view(B, KVH, t32 // 16, 16, hd // 32, 4, 8)
-  return v.permute(0, 1, 2, 4, 5, 3, 6).contiguous().view(B, KVH, t32 // 16, hd // 32, 64, 8)
-
-
-def _pack_v(v, t32):
-  B, KVH, _, hd = v.shape
-  w = _pad_t(v, t32).view(B, KVH, t32 // 32, 4, 8, hd // 16, 16)
-  return w.permute(0, 1, 5, 2, 3, 6, 4).contiguous().view(B, KVH, hd // 16, t32 // 32, 64, 8)
-
-
-def _unpack_k(kp, t32):
-  B, KVH, _, chunks = kp.shape[:4]
-  return kp.view(B, KVH, t32 // 16, chunks, 4, 16, 8).permute(0, 1, 2, 5, 3, 4, 6).reshape(B, KVH, t32, chunks * 32)
-
-
-def _unpack_v(vp, t32):
-  B, KVH, groups = vp.shape[:3]
-  return vp.view(B, KVH, groups, t32 // 32, 4, 16, 8).permute(0, 1, 3, 4, 6, 2, 5).reshape(B, KVH, t32, groups * 16)
+# Reference packers for the two fragment layouts at a general head dim: tests/attn_oracle.py
+_pack_k, _pack_v, _unpack_k, _unpack_v = ao.pack_k, ao.pack_v, ao.unpack_k, ao.unpack_v
 
 
 def _e4m3_bound(x, scale):
@@ -300,6 +270,8 @@ def _check_ragged(c, out, sls, fp8):
       assert err < 0.12 * max(ref.abs().max().item(), 1.0) + 0.05, (b, err)
     else:
       assert torch.allclose(o, ref, atol=3e-2, rtol=3e-2), (b, err)
+  if fp8:
+    assert ao.fp8_cache_worst_ratio(out, c["q"], c["kp8"], c["vp8"], c["ksc"], c["vsc"], sls) <= 1.0
 
 
 @pytest.mark.parametrize("fp8", [False, True])
@@ -348,6 +320,7 @@ def test_decode_fp8(hip, caches256, softcap, window):
     err = (f8 - other).abs().max().item()
     print(f"fp8 vs {name}: max abs err {err:.4g} (bound {bound:.4g})")
     assert err < bound, (name, err)
+  assert ao.fp8_cache_worst_ratio(f8, c["q"], c["kp8"], c["vp8"], c["ksc"], c["vsc"], [sl, sl], softcap, window) <= 1.0
 
 
 # ---------------- 6. prefill vs torch_ref ----------------

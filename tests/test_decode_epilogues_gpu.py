@@ -6,6 +6,8 @@ model's carried norm (XOT_FUSE_EPILOGUE) against the per-layer norms."""
 import pytest
 import torch
 
+from attn_oracle import pack_k as _pack_k, pack_v as _pack_v  # reference packers of the MFMA cache images
+
 pytestmark = pytest.mark.gpu
 
 HD = 128
@@ -14,24 +16,6 @@ HD = 128
 def bt(*shape, scale=1.0, seed=0):
   g = torch.Generator(device="cuda").manual_seed(seed)
   return (torch.randn(*shape, generator=g, device="cuda", dtype=torch.float32) * scale).to(torch.bfloat16)
-
-
-def _pack_k(k, t32):
-  """[B,KVH,t32,128] -> the MFMA K image [B,KVH,t32/16,4,64,8]:
-  hd = c*32 + qt*8 + j, lane = qt*16 + pos16."""
-  B, KVH, T, hd = k.shape
-  assert T == t32
-  return k.view(B, KVH, t32 // 16, 16, 4, 4, 8).permute(0, 1, 2, 4, 5, 3, 6).contiguous() \
-          .view(B, KVH, t32 // 16, 4, 64, 8)
-
-
-def _pack_v(v, t32):
-  """[B,KVH,t32,128] -> the MFMA V image [B,KVH,8,t32/32,64,8]:
-  pos = tp*32 + qt*8 + j, hd = g*16 + c16, lane = qt*16 + c16."""
-  B, KVH, T, hd = v.shape
-  assert T == t32
-  return v.view(B, KVH, t32 // 32, 4, 8, 8, 16).permute(0, 1, 5, 2, 3, 6, 4).contiguous() \
-          .view(B, KVH, 8, t32 // 32, 64, 8)
 
 
 @pytest.fixture(scope="module")

@@ -4,6 +4,8 @@ compared against the fp32 reference cast to bf16."""
 import pytest
 import torch
 
+import attn_oracle as ao
+
 pytestmark = pytest.mark.gpu
 
 
@@ -267,23 +269,8 @@ def test_moe_grouped_gpu_matches_loop():
   assert err < 3e-2, err
 
 
-def _pack_k(k, t32):
-  """Python reference packer for the MFMA K cache layout (tests only)."""
-  B, KVH, T, hd = k.shape
-  kk = torch.zeros(B, KVH, t32, hd, dtype=k.dtype, device=k.device)
-  kk[:, :, :T] = k
-  # hd = c*32 + qt*8 + j ; lane = qt*16 + pos16
-  v = kk.view(B, KVH, t32 // 16, 16, 4, 4, 8)
-  return v.permute(0, 1, 2, 4, 5, 3, 6).contiguous().view(B, KVH, t32 // 16, 4, 64, 8)
-
-
-def _pack_v(v, t32):
-  B, KVH, T, hd = v.shape
-  vv = torch.zeros(B, KVH, t32, hd, dtype=v.dtype, device=v.device)
-  vv[:, :, :T] = v
-  # pos = tp*32 + qt*8 + j ; hd = g*16 + c16 ; lane = qt*16 + c16
-  w = vv.view(B, KVH, t32 // 32, 4, 8, 8, 16)
-  return w.permute(0, 1, 5, 2, 3, 6, 4).contiguous().view(B, KVH, 8, t32 // 32, 64, 8)
+# Python reference packers of the MFMA cache layouts: tests/attn_oracle.py
+_pack_k, _pack_v, _unpack_k, _unpack_v = ao.pack_k, ao.pack_v, ao.unpack_k, ao.unpack_v
 
 
 def test_mfma16_probe(hip):
@@ -619,18 +606,7 @@ def test_gemma2_gpu_hip_path_matches_eager():
 
 # ---------------- MLA (DeepSeek) absorbed-latent decode ----------------
 
-def _mla_pack_ref(lat, rot, T32):
-  """Python reference packer for the MLA fragment layouts."""
-  B, T = lat.shape[0], lat.shape[1]
-  full = torch.cat([lat, rot], dim=-1)  # [B, T, 576]
-  kp = torch.zeros(B, T32 // 16, 18, 64, 8, dtype=lat.dtype, device=lat.device)
-  vp = torch.zeros(B, 32, T32 // 32, 64, 8, dtype=lat.dtype, device=lat.device)
-  for pos in range(T):
-    for d in range(576):
-      kp[:, pos >> 4, d >> 5, ((d & 31) >> 3) * 16 + (pos & 15), d & 7] = full[:, pos, d]
-      if d < 512:
-        vp[:, d >> 4, pos >> 5, ((pos & 31) >> 3) * 16 + (d & 15), pos & 7] = full[:, pos, d]
-  return kp, vp
+_mla_pack_ref = ao.mla_pack  # Python reference packer for the MLA fragment layouts
 
 
 def test_mla_append_layout(hip):
@@ -909,6 +885,8 @@ def test_fp8_kv_append_and_decode(hip):
   err = (out_f8 - ref).abs().max().item()
   scale_ref = ref.abs().max().item()
   assert err < 0.12 * max(scale_ref, 1.0) + 0.05, (err, scale_ref)
+  # the kernel's own arithmetic, K / V / q quantization set aside: fp64 over the dequantized cache
+  assert ao.fp8_cache_worst_ratio(out_f8, q, kp8, vp8, ksc, vsc, [S] * B) <= 1.0
 
 
 def _fp8kv_tiny_model():
@@ -1085,6 +1063,7 @@ def test_mla_fp8_decode(hip, monkeypatch):
   err = (out_8 - out_b).abs().max().item()
   ref_scale = out_b.abs().max().item()
   assert err < 0.12 * max(ref_scale, 1.0) + 0.05, (err, ref_scale)
+  assert ao.fp8_cache_worst_ratio(out_8, q8, kp_8, vp_8, ks, ks, [S] * B, sq=sq) <= 1.0
 
 
 @pytest.mark.gpu
@@ -1159,18 +1138,6 @@ def test_deepseek_yarn_gpu_matches_eager():
 
 # ---------------- attention / append paths the shared device helpers cover ----------------
 
-def _unpack_k(kp, t32):
-  """Inverse of _pack_k: [B,KVH,t32/16,4,64,8] -> [B,KVH,t32,128]."""
-  B, KVH = kp.shape[:2]
-  return kp.view(B, KVH, t32 // 16, 4, 4, 16, 8).permute(0, 1, 2, 5, 3, 4, 6).reshape(B, KVH, t32, 128)
-
-
-def _unpack_v(vp, t32):
-  """Inverse of _pack_v: [B,KVH,8,t32/32,64,8] -> [B,KVH,t32,128]."""
-  B, KVH = vp.shape[:2]
-  return vp.view(B, KVH, 8, t32 // 32, 4, 16, 8).permute(0, 1, 3, 4, 6, 2, 5).reshape(B, KVH, t32, 128)
-
-
 def _e4m3_bound(x, scale):
   """|dequant - x| bound for an e4m3 row quantized at `scale`: 3 mantissa bits
   (2^-4 relative), x itself a bf16 rounding of the quantized fp32 value
@@ -1231,6 +1198,8 @@ def test_attn_decode_mfma_prefetch_off_equals_on(hip, gqa_caches, monkeypatch, f
       assert err < 0.12 * max(ref.abs().max().item(), 1.0) + 0.05, (b, err)
     else:
       assert torch.allclose(o, ref, atol=3e-2, rtol=3e-2), (b, err)
+  if fp8:
+    assert ao.fp8_cache_worst_ratio(on, c["q"], c["kp8"], c["vp8"], c["ksc"], c["vsc"], sls) <= 1.0
 
 
 def test_fp8_kv_append_content(hip):
@@ -1307,6 +1276,7 @@ def test_attn_decode_mfma_fp8_softcap_window(hip, gqa_caches):
   err = (out - ref).abs().max().item()
   print(f"max abs err {err:.4g} ref max {ref.abs().max().item():.4g}")
   assert err < 0.12 * max(ref.abs().max().item(), 1.0) + 0.05, err
+  assert ao.fp8_cache_worst_ratio(out, c["q"], c["kp8"], c["vp8"], c["ksc"], c["vsc"], [100, 100], 30.0, 40) <= 1.0
 
 
 def test_attn_decode_mla_partial_head_group(hip):

@@ -77,7 +77,7 @@ def main():
 def attn_mfma_bench():
   import sys
   sys.path.insert(0, ".")
-  from tests.test_kernels_gpu import _pack_k, _pack_v
+  from tests.attn_oracle import pack_k as _pack_k, pack_v as _pack_v
   from xotorch_amd.ops import torch_ref
   for (B, H, KVH, T, sl) in ((64, 64, 8, 640, 576), (256, 32, 8, 640, 576)):
     hd = 128
@@ -105,7 +105,7 @@ def prefill_attn_bench():
   import sys
   from pathlib import Path
   sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-  from tests.test_kernels_gpu import _pack_k, _pack_v
+  from tests.attn_oracle import pack_k as _pack_k, pack_v as _pack_v
   import torch.nn.functional as F
   B, S, H, KVH, hd = 64, 512, 64, 8, 128
   t32 = (S + 31) // 32 * 32

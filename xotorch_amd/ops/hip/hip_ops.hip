@@ -612,12 +612,17 @@ DEVINL void attn_rescale(floatx4 (&acco)[NG], const float (&alpha)[4], float f) 
     for (int r = 0; r < 4; ++r) acco[g][r] *= alpha[r] * f;
 }
 
-// fp8 PV running scale: s_pv = the tile's V-scale ceiling; acco is kept in
-// units of 1/R so the quantized P' = p * s_v[pos] / s_pv enters at full e4m3
-// range. vs = this head's per-position V scales. Returns s_pv, sets rfac (the
-// factor that moves acco from the old R to the new) and R.
-DEVINL float attn_fp8_pv_scale(const float* __restrict__ vs, int t, int T32, int lane, float& R, float& rfac) {
-  const float s_pv = fmaxf(wave_max(vs[min(t + (lane & 31), T32 - 1)]), 1e-12f);
+// fp8 PV running scale: s_pv = the V-scale ceiling of the tile's positions
+// below vend, the tile's visible end; acco is kept in units of 1/R so the
+// quantized P' = p * s_v[pos] / s_pv enters at full e4m3 range. Positions from
+// vend on carry p = 0 and stay out of the maximum: past the sequence length a
+// fresh cache holds scale 1.0, about 250 times a real scale, which would push
+// every P' of the last tile below e4m3's smallest normal. vs = this head's
+// per-position V scales. Returns s_pv, sets rfac (the factor that moves acco
+// from the old R to the new) and R.
+DEVINL float attn_fp8_pv_scale(const float* __restrict__ vs, int t, int vend, int lane, float& R, float& rfac) {
+  const int pos = t + (lane & 31);
+  const float s_pv = fmaxf(wave_max(pos < vend ? vs[pos] : 0.f), 1e-12f);
   rfac = R / s_pv;
   R = s_pv;
   return s_pv;
@@ -626,19 +631,20 @@ DEVINL float attn_fp8_pv_scale(const float* __restrict__ vs, int t, int T32, int
 // P -> LDS image (16 rows x 32 positions, 48-element row stride: 96 B for
 // bf16, conflict-free b128 reads) and back as the PV MFMA's A fragment
 // [row = lane & 15][k = (lane >> 4) * 8 + j]. FP8 stores p * s_v[pos] / s_pv
-// as e4m3 bytes (vs / s_pv as in attn_fp8_pv_scale; unused otherwise).
+// as e4m3 bytes (vs / s_pv / vend as in attn_fp8_pv_scale; unused otherwise);
+// from vend on it stores 0 without reading the scale, whatever lies there.
 // GQA decode kernel only: the prefill and MLA kernels store through their own
 // LDS pointer — passed through a parameter, LLVM resolves the LDS address
 // space later and their loops came out 1-26% slower.
 template <bool FP8>
 DEVINL typename Frag<FP8>::T attn_p_fragment(unsigned short* plds, const floatx4 (&sc)[2], int lane,
-                                             const float* __restrict__ vs, int t, int T32, float s_pv) {
+                                             const float* __restrict__ vs, int t, int vend, float s_pv) {
   typename Frag<FP8>::E* pl = reinterpret_cast<typename Frag<FP8>::E*>(plds);
   const int col = lane & 15;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     float svv = 1.f;
-    if constexpr (FP8) svv = vs[min(t + h * 16 + col, T32 - 1)];
+    if constexpr (FP8) svv = (t + h * 16 + col < vend) ? vs[t + h * 16 + col] : 0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = ((lane >> 4) * 4 + r) * 48 + h * 16 + col;
@@ -878,9 +884,9 @@ __global__ __launch_bounds__(256, HD > 128 ? 2 : 3) void attn_decode_mfma_kernel
     }
     float alpha[4], s_pv = 1.f, rfac = 1.f;
     attn_softmax_tile(sc[0], sc[1], m, lsum, alpha);
-    if (FP8) s_pv = attn_fp8_pv_scale(vs_row, t, T32, lane, Rscale, rfac);
+    if (FP8) s_pv = attn_fp8_pv_scale(vs_row, t, c1, lane, Rscale, rfac);
     attn_rescale(acco, alpha, rfac);
-    const FT pf = attn_p_fragment<FP8>(plds, sc, lane, vs_row, t, T32, s_pv);
+    const FT pf = attn_p_fragment<FP8>(plds, sc, lane, vs_row, t, c1, s_pv);
     // issue next tile's K stream now; it completes under the PV MFMAs
     if (PREFETCH && t + 32 < c1) load_k_tile(t + 32);
     // ---- PV: out[16q][g*16..] += P x V ----
@@ -1620,7 +1626,7 @@ __global__ __launch_bounds__(256) void attn_decode_mla_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) lsum[r] = lsum[r] * alpha[r] + rsum[r];
     float s_pv = 1.f, rfac = 1.f;
-    if (FP8) s_pv = attn_fp8_pv_scale(ks + (size_t)b * T32, t, T32, lane, Rscale, rfac);
+    if (FP8) s_pv = attn_fp8_pv_scale(ks + (size_t)b * T32, t, c1, lane, Rscale, rfac);
     attn_rescale(acco, alpha, rfac);
     long pf8 = 0;
     bf16x8 pf;
@@ -1629,7 +1635,7 @@ __global__ __launch_bounds__(256) void attn_decode_mla_kernel(
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int pos = t + h * 16 + col;
-        const float svv = ks[(size_t)b * T32 + min(pos, T32 - 1)];
+        const float svv = pos < c1 ? ks[(size_t)b * T32 + pos] : 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const unsigned short pk = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(
@@ -2685,6 +2691,10 @@ torch::Tensor attn_decode_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor 
   TORCH_CHECK(GQA_PACKED_HD(hd), "attn_decode_mfma: head_dim must be 128 or 256, got ", hd);
   check_packed_gqa_shapes("attn_decode_mfma", kp, vp, hd);
   const int KVH = kp.size(1);
+  // a wave scores all H / KVH query heads of its kv head as the 16 rows of one MFMA tile
+  TORCH_CHECK(H % KVH == 0 && H / KVH <= 16,
+              "attn_decode_mfma: H must be a multiple of KVH with at most 16 query heads per kv head, got H=",
+              H, " KVH=", KVH);
   const int T32 = kp.size(2) * 16;
   const long long q_stride = q.stride(0);
   // one wave per (b, kvh, split); target >= ~2048 waves so 16 waves/CU keep
@@ -2695,7 +2705,7 @@ torch::Tensor attn_decode_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor 
   // workgroup, which then merges through LDS and writes the bf16 rows itself.
   // XOT_ATTN_FUSED_MERGE=0 (read per call) keeps the workspace + merge launch.
   const char* fm_env = getenv("XOT_ATTN_FUSED_MERGE");
-  const bool fused = (nsplit == 1 || nsplit == 2 || nsplit == 4) && H / KVH <= 16
+  const bool fused = (nsplit == 1 || nsplit == 2 || nsplit == 4)
                      && ((fm_env == nullptr) || (fm_env[0] != '0'));
   const SplitKV kv(q, q.sizes(), B * H, nsplit, hd, !fused);
   const float scale = (scale_in > 0.0) ? (float)scale_in : 1.0f / sqrtf((float)hd);
