@@ -356,6 +356,8 @@ class DeepseekV3Model(ShardBase):
         mod.pack_decode()
         if mod.weight_packed is not None:
           packed += mod.weight_packed.numel() * 2
+        elif mod.weight_packed_w4 is not None:  # XOT_W4_GEMM=1; the routed experts below stay bf16
+          packed += mod.weight_packed_w4.numel() + mod.weight_scale_w4.numel()
     for mod in self.modules():
       if isinstance(mod, DsMoE):
         mod.pack_grouped()

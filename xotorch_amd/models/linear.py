@@ -16,7 +16,8 @@ from xotorch_amd import ops
 
 # key -> the route that won when timed in-situ (first eligible call, before
 # hipGraph capture); seed it to force a route. (N, K, M) -> "packed" | "xreg" |
-# "blaslt" for a GEMM, ("fuse_swiglu", N, I, M) -> "fused" | "split" for the MLP.
+# "blaslt" for a GEMM, ("w4", N, K, M) -> "mxfp4" | "blaslt" for one in MXFP4
+# mode, ("fuse_swiglu", N, I, M) -> "fused" | "split" for the MLP.
 DECODE_PICKS: dict = {}
 
 
@@ -91,6 +92,9 @@ class XotLinear(nn.Linear):
     self.weight_packed = None
     self.weight_packed_fp8 = None
     self.weight_scale = None
+    self.weight_packed_w4 = None  # MXFP4 code image (ops.pack_decode_weight_mxfp4)
+    self.weight_scale_w4 = None   # its e8m0 scale image
+    self.keep_bf16 = False  # W4 mode leaves this module's weight and pack in bf16 (lm_head)
     self._w8 = None  # lazily cached fp8 prefill copy (_fp8_prefill)
     self._w8_scale = None
 
@@ -100,15 +104,29 @@ class XotLinear(nn.Linear):
 
   def pack_decode(self):
     if self.packable() and self.weight.is_cuda and self.weight.dtype == torch.bfloat16:
-      if ops.fp8_gemm_enabled():
-        if self.weight_packed_fp8 is None:
-          self.weight_packed_fp8, self.weight_scale = ops.pack_decode_weight_fp8(self.weight.detach())
-      elif self.weight_packed is None:
-        self.weight_packed = ops.pack_decode_weight(self.weight.detach())
+      self._pack()
+
+  def _pack(self):
+    """The pack of the format the environment selects. MXFP4 also writes the
+    dequantized weight back into `weight`: prefill, the hipBLASLt arm and the
+    W4 kernel then serve the same quantized model."""
+    fmt = ops.decode_weight_format()
+    if fmt == "fp8":
+      if self.weight_packed_fp8 is None:
+        self.weight_packed_fp8, self.weight_scale = ops.pack_decode_weight_fp8(self.weight.detach())
+    elif fmt == "mxfp4" and not self.keep_bf16:
+      if self.weight_packed_w4 is None:
+        self.weight_packed_w4, self.weight_scale_w4, w_dq = ops.pack_decode_weight_mxfp4(self.weight.detach())
+        with torch.no_grad():
+          self.weight.copy_(w_dq)
+    elif self.weight_packed is None:
+      self.weight_packed = ops.pack_decode_weight(self.weight.detach())
 
   def unpack_decode(self):
     self.weight_packed = None
     self.weight_packed_fp8 = None
+    self.weight_packed_w4 = None
+    self.weight_scale_w4 = None
 
   def _fp8_prefill(self, x):
     """Opt-in (XOT_FP8_PREFILL=1) e4m3 prefill GEMM via hipBLASLt scaled_mm:
@@ -156,14 +174,25 @@ class XotLinear(nn.Linear):
           return self._fp8_prefill(x)
         except torch.cuda.OutOfMemoryError:
           torch.cuda.empty_cache()  # fall back to the bf16 path
-    wp, wp8 = self.weight_packed, self.weight_packed_fp8
-    if wp is not None or wp8 is not None:
+    wp, wp8, wq = self.weight_packed, self.weight_packed_fp8, self.weight_packed_w4
+    if wp is not None or wp8 is not None or wq is not None:
       N, K = self.weight.shape
       M = decode_rows(x, K)
       if M and wp8 is not None:
         x8, sx = ops.quant_fp8_rows(x.view(M, K))
         y = ops.skinny_gemm_fp8(x8, sx, wp8, self.weight_scale, 1, N, self.bias)
         return y.view(list(x.shape[:-1]) + [N])
+      if M and wq is not None:
+        # `weight` holds the dequantized values (pack_decode), so the library
+        # arm computes the same model; it keeps the shapes where 4-bit loses
+        b, ws = self.bias, self.weight_scale_w4
+        use = auto_pick(("w4", N, K, M), "w4-gemm", "NKM", 0.95, lambda: [
+          ("blaslt", lambda: torch.nn.functional.linear(x, self.weight, b)),
+          ("mxfp4", lambda: ops.skinny_gemm_mxfp4(x, wq, ws, 1, N, b))])
+        if use == "mxfp4":
+          if epilogue is not None:
+            return ops.skinny_gemm_mxfp4_epilogue(x, wq, ws, N, b, epilogue)
+          return ops.skinny_gemm_mxfp4(x, wq, ws, 1, N, b)
       if M and wp is not None:
         b = self.bias
         use = auto_pick((N, K, M), "gemm", "NKM", 0.95, lambda: [

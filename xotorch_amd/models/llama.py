@@ -159,9 +159,23 @@ class MoEMLP(nn.Module):
     self.wp_down_fp8: Optional[torch.Tensor] = None
     self.sw_gate_up: Optional[torch.Tensor] = None
     self.sw_down: Optional[torch.Tensor] = None
+    self.wq_gate_up: Optional[torch.Tensor] = None  # MXFP4: stacked code images, scales in sw_*
+    self.wq_down: Optional[torch.Tensor] = None
 
   def pack_grouped(self):
     """Stack the experts' prepacked weights for the grouped decode GEMM."""
+    if ops.w4_gemm_enabled():
+      if self.wq_gate_up is None \
+         and all(getattr(e.gate_up_proj, "weight_packed_w4", None) is not None for e in self.experts) \
+         and all(getattr(e.down_proj, "weight_packed_w4", None) is not None for e in self.experts):
+        self.wq_gate_up = torch.stack([e.gate_up_proj.weight_packed_w4 for e in self.experts]).contiguous()
+        self.sw_gate_up = torch.stack([e.gate_up_proj.weight_scale_w4 for e in self.experts]).contiguous()
+        self.wq_down = torch.stack([e.down_proj.weight_packed_w4 for e in self.experts]).contiguous()
+        self.sw_down = torch.stack([e.down_proj.weight_scale_w4 for e in self.experts]).contiguous()
+        for e in self.experts:  # the stacks supersede the per-expert images
+          e.gate_up_proj.weight_packed_w4 = e.gate_up_proj.weight_scale_w4 = None
+          e.down_proj.weight_packed_w4 = e.down_proj.weight_scale_w4 = None
+      return
     if ops.fp8_gemm_enabled():
       if self.wp_gate_up_fp8 is None \
          and all(getattr(e.gate_up_proj, "weight_packed_fp8", None) is not None for e in self.experts) \
@@ -211,7 +225,9 @@ class MoEMLP(nn.Module):
       selected, weights = ops.moe_route(self.gate(flat).float().contiguous(), None, self.top_k, 0)
     else:
       weights, selected = self._route(flat)                   # [T, k]
-    if self.wp_gate_up_fp8 is not None:
+    if self.wq_gate_up is not None:
+      packs = (self.wq_gate_up, self.wq_down, (self.sw_gate_up, self.sw_down), True)
+    elif self.wp_gate_up_fp8 is not None:
       packs = (self.wp_gate_up_fp8, self.wp_down_fp8, (self.sw_gate_up, self.sw_down))
     else:
       packs = (self.wp_gate_up, self.wp_down)
@@ -276,6 +292,7 @@ def pack_decode_weights(model, reserve_bytes: int) -> int:
   of its modules stay on hipBLASLt. Returns bytes packed. Policy override:
   XOT_PACK=none|down|all."""
   mode = os.getenv("XOT_PACK", "auto")
+  fmt = ops.decode_weight_format()  # raises when both XOT_FP8_GEMM and XOT_W4_GEMM are set
   if mode == "none" or not torch.cuda.is_available():
     return 0
   groups: List[List[XotLinear]] = [[], [], [], []]
@@ -297,26 +314,32 @@ def pack_decode_weights(model, reserve_bytes: int) -> int:
       groups[2].append(mod)
     else:  # qkv_proj / o_proj / experts' projections
       groups[3].append(mod)
-  if mode != "all" and not ops.fp8_gemm_enabled():
+  if mode != "all" and fmt == "bf16":
     # default (bf16): the measured winners — down_proj (tuned hipBLASLt
     # 110 us vs 84.6 packed at 70B decode shapes), lm_head (5.3 -> 6.2
     # TB/s), gate_up (175.5 vs 178.9 us); qkv/o measure tied on hipBLASLt
-    # — not worth the second weight copy. In fp8 mode every group wins
-    # (half the stream bytes), so all are packed.
+    # — not worth the second weight copy. In fp8 and MXFP4 mode every group
+    # packs (half and about a quarter of the stream bytes).
     groups = groups[:3]
+  if fmt == "mxfp4":
+    # lm_head is never quantized: it may be tied to the embedding, and 4-bit
+    # logits are a quality decision of their own. It keeps its bf16 pack.
+    for m in groups[1]:
+      m.keep_bf16 = True
+  fmt_bytes = {"bf16": 2, "fp8": 1, "mxfp4": 17 / 32}[fmt]  # mxfp4: a nibble + one scale byte per 32
   packed = 0
   debug = os.getenv("XOT_DEBUG", "0") != "0"
   free_bytes = lambda: torch.cuda.mem_get_info()[0]
   for gi, grp in enumerate(groups):
     if not grp:
       continue
-    bytes_per = 1 if ops.fp8_gemm_enabled() else 2
-    need = sum(m.weight.numel() * bytes_per for m in grp)
+    bytes_per = 2 if fmt == "mxfp4" and gi == 1 else fmt_bytes
+    need = int(sum(m.weight.numel() * bytes_per for m in grp))
     free = free_bytes()
     if need + reserve_bytes > free:
       # MoE experts pack all or none: the grouped stack needs every expert
       n = 0 if any(m in experts for m in grp) else pack_group_partial(grp, bytes_per, reserve_bytes, free_bytes)
-      packed += sum(m.weight.numel() * bytes_per for m in grp[:n])
+      packed += int(sum(m.weight.numel() * bytes_per for m in grp[:n]))
       if debug:
         print(f"[xot] pack group {gi}: packed {n} of {len(grp)} modules (need {need>>20} MiB + reserve "
               f"{reserve_bytes>>20} MiB > free {free>>20} MiB)", flush=True)

@@ -8,13 +8,15 @@ from xotorch_amd import ops
 
 
 def moe_decode(flat, selected, weights, E: int, I: int, experts, wp_gate_up=None, wp_down=None,
-               scales=None):
+               scales=None, mxfp4: bool = False):
   """Static-shape (hipGraph-capturable) routed experts on flat [T, D] with
   expert ids / weights [T, k]: assignments are sorted by expert, every expert
   gets the fixed capacity C (top-k experts are distinct per token, so one
   expert receives at most T assignments: lossless), padded slots weigh 0.
   With stacked packs [E, ...] each expert GEMM is ONE grouped launch, bf16 or
-  (scales = (sw_gate_up, sw_down)) fp8; without, experts[e] runs on its slice.
+  (scales = (sw_gate_up, sw_down)) fp8, or MXFP4 weight-only (mxfp4: the packs
+  are the stacked code images and scales the stacked e8m0 images); without,
+  experts[e] runs on its slice.
   Returns [T, D]: bf16 from the HIP combine, fp32 from the torch one."""
   T, D = flat.shape
   C = max(32, -(-T // 32) * 32)
@@ -42,6 +44,10 @@ def moe_decode(flat, selected, weights, E: int, I: int, experts, wp_gate_up=None
   xg = flat[gather_tok]                                     # [E*C, D]
   if wp_gate_up is None or torch.is_grad_enabled():
     y = torch.cat([experts[e](xe) for e, xe in enumerate(xg.view(E, C, D))], dim=0)
+  elif mxfp4:
+    gu = ops.skinny_gemm_mxfp4(xg.view(E, C, D), wp_gate_up, scales[0], E, 2 * I)
+    h = ops.swiglu_packed(gu.view(E * C, 2 * I))
+    y = ops.skinny_gemm_mxfp4(h.view(E, C, I), wp_down, scales[1], E, D)
   elif scales is not None:
     x8, sx = ops.quant_fp8_rows(xg)
     gu = ops.skinny_gemm_fp8(x8, sx, wp_gate_up, scales[0].view(-1), E, 2 * I)

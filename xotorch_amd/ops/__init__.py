@@ -220,6 +220,8 @@ skinny_gemm_packed_swiglu = _binding("skinny_gemm_packed_swiglu")  # (gu [.., 2I
 skinny_gemm_grouped = _binding("skinny_gemm_grouped")  # (x [E, C, K], stacked wp, E, N) -> [E, C, N]
 quant_fp8_rows = _binding("quant_fp8_rows")            # (x [M, K]) -> (e4m3 bytes [M, K], fp32 row scales [M])
 skinny_gemm_fp8 = _binding("skinny_gemm_fp8")          # (x8, sx, wp8, sw, E, N[, bias]): W8A8, grouped when E > 1
+# (x, wq, ws, E, N[, bias]): W4A16 on the MXFP4 images of pack_decode_weight_mxfp4, grouped when E > 1
+skinny_gemm_mxfp4 = _binding("skinny_gemm_mxfp4")
 # (fp32 logits [T, E], bias | None, k, mode[, n_group, topk_group, routed_scale, norm_topk]) -> (ids [T, k]
 # int32, weights [T, k] fp32); mode 0 softmax-topk-renorm, mode 1 sigmoid + group-limited top-k
 moe_route = _binding("moe_route")
@@ -249,6 +251,11 @@ def skinny_gemm_packed_swiglu_epilogue(gu, wp, N: int, bias, epilogue):
   return _packed_epilogue(_gpu().skinny_gemm_packed_swiglu_epilogue, gu, wp, N, bias, epilogue)
 
 
+def skinny_gemm_mxfp4_epilogue(x, wq, ws, N: int, bias, epilogue):
+  fn = lambda x, wq, *rest: _gpu().skinny_gemm_mxfp4_epilogue(x, wq, ws, *rest)
+  return _packed_epilogue(fn, x, wq, N, bias, epilogue)
+
+
 def pack_decode_weight(w: torch.Tensor) -> torch.Tensor:
   """Pre-shuffle a [N, K] bf16 weight into MFMA A-fragment order for the
   packed skinny decode GEMM: [N/32, K/16, 64 lanes, 8 bf16] with lane =
@@ -274,6 +281,83 @@ def pack_decode_weight_fp8(w: torch.Tensor):
 
 def fp8_gemm_enabled() -> bool:
   return os.getenv("XOT_FP8_GEMM", "0") == "1"
+
+
+# ---- MXFP4 (OCP microscaling): e2m1 elements, one e8m0 scale per 32 along K.
+# A code is one nibble: bit 3 the sign, bits 2:0 the index into MXFP4_GRID.
+MXFP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MXFP4_BLOCK = 32
+
+
+def w4_gemm_enabled() -> bool:
+  """XOT_W4_GEMM (default 0): MXFP4 weight-only (W4A16) decode GEMMs."""
+  return os.getenv("XOT_W4_GEMM", "0") == "1"
+
+
+def decode_weight_format() -> str:
+  """The packed decode weight format the environment asks for: "bf16", "fp8"
+  (XOT_FP8_GEMM=1) or "mxfp4" (XOT_W4_GEMM=1); both knobs together are an error."""
+  if fp8_gemm_enabled() and w4_gemm_enabled():
+    raise RuntimeError("XOT_FP8_GEMM=1 and XOT_W4_GEMM=1 are exclusive: choose one decode weight format")
+  return "fp8" if fp8_gemm_enabled() else "mxfp4" if w4_gemm_enabled() else "bf16"
+
+
+def quant_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+  """[N, K] -> (codes uint8 [N, K], one per byte, e8 uint8 [N, K/32]). Per
+  32-block the OCP rule: e = floor(log2(amax)) - 2 clamped to [-125, 125]
+  (every dequantized value a normal bf16, the scale a normal fp32), stored as
+  e + 127; elements are w / 2^e rounded to the nearest grid value, ties to
+  the even code, saturating at +-6. An all-zero block stores 127."""
+  N, K = w.shape
+  assert N % 32 == 0 and K % 64 == 0, (N, K)
+  wb = w.detach().float().view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+  amax = wb.abs().amax(dim=-1)
+  _, ex = torch.frexp(amax)  # amax = m * 2^ex with m in [0.5, 1): floor(log2) = ex - 1
+  e = torch.where(amax > 0, ex - 3, torch.zeros_like(ex)).clamp(-125, 125)
+  a = torch.ldexp(wb.abs(), -e.unsqueeze(-1))  # exact: a power-of-two scale
+  # one threshold per midpoint; a tie goes up only where the upper code is even
+  idx = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75)
+         + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+  codes = idx | (torch.signbit(wb).to(torch.uint8) << 3)
+  return codes.view(N, K).contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequant_mxfp4(codes: torch.Tensor, e8: torch.Tensor) -> torch.Tensor:
+  """The definition: fp32 [N, K] = (-1)^bit3 * MXFP4_GRID[bits 2:0] * 2^(e8 - 127)."""
+  N, K = codes.shape
+  grid = torch.tensor(MXFP4_GRID, dtype=torch.float32, device=codes.device)
+  mag = grid[(codes & 7).long()]
+  val = torch.where((codes & 8) != 0, -mag, mag).view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+  return torch.ldexp(val, (e8.to(torch.int32) - 127).unsqueeze(-1)).view(N, K)
+
+
+def pack_decode_weight_mxfp4(w: torch.Tensor):
+  """Quantize a [N, K] weight to MXFP4 and shuffle it into the two images the
+  W4A16 decode GEMM streams (stated once beside skinny_gemm_packed_kernel):
+  wq uint8 [N/32, K/64, 64 lanes, 16 B] (lane = (k-half)*32 + n-row; dword u
+  = the lane's 8 codes of k16-chunk u, lower k in the lower nibble) and ws
+  uint8 [N/32, K/64, 32 rows, 2] (the two e8m0 scales of that 64-k step).
+  Returns (wq, ws, w_dq): w_dq = the dequantized weight in bf16, exact.
+  17/32 byte per weight against 2 for the bf16 prepack (XOT_W4_GEMM=1)."""
+  N, K = w.shape
+  rows = 4096  # both images are row-tile major: bound the fp32 temporaries of a large weight
+  if N > rows:
+    parts = [pack_decode_weight_mxfp4(w[r:r + rows]) for r in range(0, N, rows)]
+    return tuple(torch.cat(p) for p in zip(*parts))
+  codes, e8 = quant_mxfp4(w)
+  w_dq = dequant_mxfp4(codes, e8).to(torch.bfloat16)
+  nib = (codes[:, 0::2] | (codes[:, 1::2] << 4)).view(N // 32, 32, K // 64, 4, 2, 4)  # [.., u, k-half, byte]
+  wq = nib.permute(0, 2, 4, 1, 3, 5).reshape(N // 32, K // 64, 64, 16).contiguous()
+  ws = e8.view(N // 32, 32, K // 64, 2).permute(0, 2, 1, 3).contiguous()
+  return wq, ws, w_dq
+
+
+def unpack_decode_weight_mxfp4(wq: torch.Tensor, ws: torch.Tensor, N: int, K: int):
+  """Inverse of the pack: (wq, ws) -> (codes [N, K], e8 [N, K/32])."""
+  nib = wq.view(N // 32, K // 64, 2, 32, 4, 4).permute(0, 3, 1, 4, 2, 5).reshape(N, K // 2)
+  codes = torch.stack([nib & 15, nib >> 4], dim=-1).view(N, K)
+  e8 = ws.view(N // 32, K // 64, 32, 2).permute(0, 2, 1, 3).reshape(N, K // 32)
+  return codes.contiguous(), e8.contiguous()
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -39,6 +39,7 @@
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float floatx16;
 typedef __attribute__((ext_vector_type(4))) float floatx4;
+typedef __attribute__((ext_vector_type(4))) unsigned int uintx4;
 
 typedef __attribute__((ext_vector_type(8))) unsigned short ushort8;
 typedef __attribute__((ext_vector_type(4))) unsigned short ushort4_t;
@@ -1928,12 +1929,51 @@ DEVINL ushort8 skinny_stage_load(const unsigned short* p, long long K) {
 // double-buffered so a K-step costs one barrier. Each wave's A stream, its
 // accumulators and its MFMA order are the same in both, and the launcher keeps
 // nsplit and kc, so both give the same bits.
-template <int MT, bool SPLIT, int BK, bool SWIGLU = false, int NW = 4>
+//
+// W4 = the MXFP4 weight-only A stream (W4A16): OCP e2m1 codes, two per byte,
+// with one e8m0 scale per 32 elements along K. The ONE definition of its two
+// images (ops.pack_decode_weight_mxfp4 writes them, the CPU test states them
+// independently):
+//   code image  [N/32][K/64][lane 0..63][16 B], lane = (k-half)*32 + n-row
+//     dword u (0..3) of a lane = its 8 elements of k16-chunk u, i.e.
+//     k = kstep*64 + u*16 + (k-half)*8 + j, element j in nibble j (lower k in
+//     the lower nibble). One 64-k step of a 32-row tile is one coalesced 1 KB
+//     wave load (a dwordx4 per lane) and each MFMA A fragment is one dword.
+//   scale image [N/32][K/64][n-row 0..31][2 B]: byte i = the e8m0 exponent of
+//     the row's 32-block i of that 64-k step (chunks 0,1 -> byte 0; 2,3 -> 1).
+//     One 64 B wave load per 64-k step; both k-halves read the same bytes.
+// A fragment is dequantized in registers (w4_frag: four packed converts), the
+// values are exact in bf16, and everything after the A operand, staging,
+// barriers, MFMA order and store, is the bf16 instantiation's, so the result
+// has the bits of the bf16 kernel on the dequantized weight. The step's loads
+// are a quarter of the bf16 stream's bytes and the whole ring is a few VGPRs, so
+// it holds W4_DEPTH steps: 4 KB per wave in flight. Measured (docs/PERF.md): 2 KB
+// to 16 KB per wave agree within 3 % on the 70B gate_up and down shapes, so the
+// bytes in flight are not what bounds this kernel; 4 KB runs qkv at M=128 15 %
+// faster than 8 KB (fewer VGPRs) and is inside that band everywhere else.
+template <int BK>
+constexpr int W4_DEPTH = 256 / BK;  // 4 steps at BK=64, 2 at BK=128
+
+// one dword of the code image (8 e2m1 codes) times 2^(e8 - 127) -> A fragment
+DEVINL bf16x8 w4_frag(unsigned int q, float scale) {
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+  const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 0);
+  const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 1);
+  const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 2);
+  const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 3);
+  return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+
+// e8m0 byte -> fp32 2^(e8 - 127); the pack keeps e8 in [2, 252], a normal fp32
+DEVINL float e8m0_scale(unsigned int e8) { return __uint_as_float(e8 << 23); }
+
+template <int MT, bool SPLIT, int BK, bool SWIGLU = false, int NW = 4, bool W4 = false>
 __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(
     const unsigned short* __restrict__ Wp, const unsigned short* __restrict__ X,
     unsigned short* __restrict__ Y, float* __restrict__ P,
     const unsigned short* __restrict__ bias,
-    int N, long long K, int kc, int nsplit, long long ldx = 0) {
+    int N, long long K, int kc, int nsplit, long long ldx = 0,
+    const unsigned char* __restrict__ Ws = nullptr) {
   // SWIGLU: X is the fused [rows, 2K] gate|up GEMM output; the staging
   // computes silu(gate)*up on the fly (row stride ldx = 2K, up at +K) —
   // the intermediate activation tensor never exists (saves its write +
@@ -1950,7 +1990,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(
   // grouped mode: expert blockIdx.y owns rows [e*MT*32, (e+1)*MT*32) of X/Y
   // and its own weight block; gridDim.y == 1 degenerates to the plain GEMM.
   const int e = blockIdx.y;
-  Wp += (size_t)e * (size_t)N * (size_t)K;
+  if (!W4) Wp += (size_t)e * (size_t)N * (size_t)K;
   X += (size_t)e * (size_t)(MT * 32) * (size_t)K;
   const long long k0 = (long long)split * kc;
   const long long k1 = min(k0 + (long long)kc, K);
@@ -1979,6 +2019,18 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(
   const int nsteps = (int)((k1 - k0) >> (BK == 64 ? 6 : 7));
   ushort8 xv[PPT];
   bf16x8 a_buf[2][BKC];
+  // W4: the ring of code dwordx4 and scale pairs, one of each per 64 k
+  constexpr int QD = W4_DEPTH<BK>;
+  constexpr int QH = BK / 64;
+  uintx4 q_buf[QD][QH];
+  unsigned int s_buf[QD][QH];
+  const unsigned char* wq = nullptr;
+  const unsigned char* wsc = nullptr;
+  if (W4) {
+    const size_t step64 = ((size_t)e * (N >> 5) + n32) * (size_t)(K >> 6) + (size_t)(k0 >> 6);
+    wq = reinterpret_cast<const unsigned char*>(Wp) + step64 * 1024 + (size_t)lane * 16;
+    wsc = Ws + step64 * 64 + (size_t)(lane & 31) * 2;
+  }
   // per-thread staging base + uniform per-piece offsets: piece p = tid+i*NT
   // has row = tid/(BK/8) + i*ROWS_PER_I and column-piece q = tid%(BK/8), so
   // one VGPR pointer plus SGPR/immediate strides replaces the old per-piece
@@ -1998,17 +2050,39 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(
     if (i < PPT - 1 || tail_ok)                                                                \
       *(ushort8*)(xs + (IMG) * XIMG + xsb + i * ROWS_PER_I * XROW) = xv[i];
 
+  // W4: ring slot BUF <- the step that starts OFF64 64-k chunks past wq / wsc.
+  // The codes are read once per launch (non-temporal); two steps' scales share
+  // a 128 B line, so those loads stay cached.
+#define SGP_W4_LOAD(BUF, OFF64)                                                                \
+  _Pragma("unroll")                                                                            \
+  for (int h = 0; h < QH; ++h) {                                                               \
+    q_buf[BUF][h] = __builtin_nontemporal_load(                                                \
+        reinterpret_cast<const uintx4*>(wq + ((OFF64) + h) * 1024));                           \
+    s_buf[BUF][h] = *reinterpret_cast<const unsigned short*>(wsc + ((OFF64) + h) * 64);        \
+  }
+
   // prologue: stage step 0, preload A(0) and A(1).  The W stream is read
   // exactly once per launch -> non-temporal (L1-bypass) loads; depth-2
   // prefetch keeps 2*BK*32n*2B per wave in flight across staging barriers.
   const unsigned short* wp1 = (nsteps > 1) ? wp + BKC * 512 : wp;  // clamp: no OOB at nsteps==1
   SGP_XLOAD(0)
+  if constexpr (W4) {
+    // steps 0 .. QD-1, clamped to the last step of a short split (no OOB)
 #pragma unroll
-  for (int u = 0; u < BKC; ++u) {
-    a_buf[0][u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wp + u * 512));
-    a_buf[1][u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wp1 + u * 512));
+    for (int d = 0; d < QD; ++d) {
+      const int sd = min(d, nsteps - 1);
+      SGP_W4_LOAD(d, (size_t)sd * QH)
+    }
+    wq += (size_t)QD * QH * 1024;
+    wsc += (size_t)QD * QH * 64;
+  } else {
+#pragma unroll
+    for (int u = 0; u < BKC; ++u) {
+      a_buf[0][u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wp + u * 512));
+      a_buf[1][u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wp1 + u * 512));
+    }
+    wp += 2 * BKC * 512;
   }
-  wp += 2 * BKC * 512;
   SGP_XSTORE(0)
   __syncthreads();
 
@@ -2037,22 +2111,67 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(
         a_buf[BUF][u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wp + u * 512)); \
       wp += BKC * 512;                                                                         \
     }                                                                                          \
+    SGP_STEP_TAIL(BUF)                                                                         \
+  }
+  // the same step on ring slot BUF (= s % QD, QD even) of the W4 stream
+#define SGP_STEP_W4(BUF)                                                                       \
+  {                                                                                            \
+    constexpr int RD = XBUFS == 2 ? ((BUF) & 1) : 0;                                           \
+    const bool last = (s == nsteps - 1);                                                       \
+    if (!last) { SGP_XLOAD(s + 1) }                                                            \
+    _Pragma("unroll")                                                                          \
+    for (int u = 0; u < BKC; ++u) {                                                            \
+      const unsigned int sp = s_buf[BUF][u >> 2];                                              \
+      const bf16x8 a = w4_frag(q_buf[BUF][u >> 2][u & 3],                                      \
+                               e8m0_scale((u & 2) ? sp >> 8 : sp & 0xffu));                    \
+      _Pragma("unroll")                                                                        \
+      for (int t = 0; t < MT; ++t) {                                                           \
+        const bf16x8 b = *reinterpret_cast<const bf16x8*>(                                     \
+            xs + RD * XIMG + t * 32 * XROW + (lane & 31) * XROW + u * 16 + (lane >> 5) * 8);   \
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[t], 0, 0, 0);               \
+      }                                                                                        \
+    }                                                                                          \
+    if (s + QD < nsteps) {                                                                     \
+      SGP_W4_LOAD(BUF, (size_t)0)                                                              \
+      wq += QH * 1024;                                                                         \
+      wsc += QH * 64;                                                                          \
+    }                                                                                          \
+    SGP_STEP_TAIL((BUF) & 1)                                                                   \
+  }
+  // staging tail of a step that read LDS image BUF: fill the image of step s+1
+#define SGP_STEP_TAIL(BUF)                                                                   \
     if (!last) {                                                                               \
       if (XBUFS == 1) __syncthreads();                                                         \
       SGP_XSTORE(XBUFS == 2 ? 1 - (BUF) : 0)                                                   \
       __syncthreads();                                                                         \
-    }                                                                                          \
-  }
+    }
 
   int s = 0;
-  while (s + 2 <= nsteps) {
-    SGP_STEP(0);
-    ++s;
-    SGP_STEP(1);
-    ++s;
+  if constexpr (W4) {
+    // QD steps per trip, one per ring slot, then the up to QD-1 left over
+#define SGP_W4_ITER(BUF) { SGP_STEP_W4(BUF) ++s; }
+#define SGP_W4_REST(BUF) if (s < nsteps) SGP_W4_ITER(BUF)
+    while (s + QD <= nsteps) {
+      SGP_W4_ITER(0) SGP_W4_ITER(1)
+      if constexpr (QD == 4) { SGP_W4_ITER(2) SGP_W4_ITER(3) }
+    }
+    SGP_W4_REST(0)
+    if constexpr (QD == 4) { SGP_W4_REST(1) SGP_W4_REST(2) }
+#undef SGP_W4_ITER
+#undef SGP_W4_REST
+  } else {
+    while (s + 2 <= nsteps) {
+      SGP_STEP(0);
+      ++s;
+      SGP_STEP(1);
+      ++s;
+    }
+    if (s < nsteps) SGP_STEP(0);
   }
-  if (s < nsteps) SGP_STEP(0);
 #undef SGP_STEP
+#undef SGP_STEP_W4
+#undef SGP_STEP_TAIL
+#undef SGP_W4_LOAD
 #undef SGP_XLOAD
 #undef SGP_XSTORE
 
@@ -3304,6 +3423,53 @@ torch::Tensor skinny_gemm_grouped(torch::Tensor x, torch::Tensor wp, int64_t E, 
   });
 }
 
+// MXFP4 weight-only (W4A16) decode GEMM on the two images of
+// ops.pack_decode_weight_mxfp4: wq [E][N/32][K/64][64][16] code bytes, ws
+// [E][N/32][K/64][32][2] e8m0 bytes. E == 1: x [.., K] bf16 -> [.., N];
+// E > 1: grouped, x [E, C, K] -> [E, C, N]. Same plan, tiles and bits as
+// skinny_gemm_packed / skinny_gemm_grouped on the dequantized weight.
+static torch::Tensor skinny_gemm_mxfp4_impl(const torch::Tensor& x, const torch::Tensor& wq,
+                                           const torch::Tensor& ws, int64_t E, int64_t N,
+                                           const c10::optional<torch::Tensor>& bias,
+                                           SkinnyEpilogue* epi) {
+  CHK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.is_contiguous());
+  CHK(wq.is_cuda() && wq.dtype() == torch::kUInt8 && wq.is_contiguous());
+  CHK(ws.is_cuda() && ws.dtype() == torch::kUInt8 && ws.is_contiguous());
+  CHK(E >= 1 && E <= 256 && N >= 128 && N % 128 == 0);
+  const long long K = x.size(-1);
+  CHK(K % 64 == 0 && wq.numel() * 2 == E * N * K && ws.numel() * 32 == E * N * K);
+  const long long M = x.numel() / (K * E);  // rows per expert
+  CHK(M >= 32 && M <= 256 && M % 32 == 0 && x.numel() == E * M * K);
+  std::vector<int64_t> sizes = x.sizes().vec();
+  if (E > 1) sizes = {(long)E, (long)M, (long)N};
+  else sizes.back() = (long)N;
+  return skinny_run<true>(x, sizes, M, N, K, E, bias, 64,
+                          [&](auto mt, auto split, auto bk, auto nw, const SkinnyLaunch& L) {
+    hipLaunchKernelGGL((skinny_gemm_packed_kernel<mt.value, split.value, bk.value, false, nw.value, true>),
+                       L.grid, dim3(nw.value * 64), 0, L.stream,
+                       (const unsigned short*)wq.data_ptr(), (const unsigned short*)x.data_ptr(),
+                       L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit, 0LL,
+                       (const unsigned char*)ws.data_ptr());
+  }, epi);
+}
+
+torch::Tensor skinny_gemm_mxfp4(torch::Tensor x, torch::Tensor wq, torch::Tensor ws, int64_t E,
+                                int64_t N, c10::optional<torch::Tensor> bias) {
+  return skinny_gemm_mxfp4_impl(x, wq, ws, E, N, bias, nullptr);
+}
+
+// skinny_gemm_mxfp4 (E = 1) + row epilogue (see skinny_gemm_packed_epilogue)
+std::vector<torch::Tensor> skinny_gemm_mxfp4_epilogue(torch::Tensor x, torch::Tensor wq,
+                                                      torch::Tensor ws, int64_t N,
+                                                      c10::optional<torch::Tensor> bias,
+                                                      torch::Tensor res,
+                                                      c10::optional<torch::Tensor> norm_w,
+                                                      double eps, double w_bias) {
+  SkinnyEpilogue epi{res, norm_w, eps, w_bias};
+  skinny_gemm_mxfp4_impl(x, wq, ws, 1, N, bias, &epi);
+  return epi.outputs();
+}
+
 // x: [M, K] bf16 -> (x8 uint8 [M, K], s_x fp32 [M])
 std::vector<torch::Tensor> quant_fp8_rows(torch::Tensor x) {
   CHK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.is_contiguous());
@@ -3374,6 +3540,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_grouped", &skinny_gemm_grouped,
         "MoE grouped decode GEMM on stacked prepacked expert weights",
         py::arg("x"), py::arg("wp"), py::arg("n_experts"), py::arg("n"));
+  m.def("skinny_gemm_mxfp4", &skinny_gemm_mxfp4,
+        "W4A16 MXFP4 decode GEMM on packed e2m1 codes + e8m0 block scales; grouped when n_experts > 1",
+        py::arg("x"), py::arg("wq"), py::arg("ws"), py::arg("n_experts"), py::arg("n"),
+        py::arg("bias") = py::none());
+  m.def("skinny_gemm_mxfp4_epilogue", &skinny_gemm_mxfp4_epilogue,
+        "skinny_gemm_mxfp4 + fused combine / residual add / following RMSNorm -> [h', normed]",
+        py::arg("x"), py::arg("wq"), py::arg("ws"), py::arg("n"), py::arg("bias"), py::arg("res"),
+        py::arg("norm_w") = py::none(), py::arg("eps") = 1e-6, py::arg("w_bias") = 0.0);
   m.def("swiglu_packed", &swiglu_packed, "SwiGLU on the packed [gate|up] GEMM output");
   m.def("geglu_packed", &geglu_packed, "GeGLU (tanh gelu) on the packed [gate|up] GEMM output");
   m.def("rmsnorm", &rmsnorm, "RMSNorm (bf16, CDNA4); w_bias=1 gives gemma-style (1+w)",
