@@ -6,6 +6,10 @@ tile exists for M >= 128 and N % 256 == 0; elsewhere XOT_SKINNY_BN=256 runs the
 128-row tile and the two columns agree. The mxfp4 column runs the weight
 quantized to MXFP4 (its own default tile); TB/s always counts the bf16 bytes
 of the weight, so the mxfp4 figure is bf16-equivalent, not bytes moved.
+Every gate_up shape also gets a "+swiglu" row per M: the packed GEMM plus
+swiglu_packed, the GEMM with SwiGLU in its store (GLU-interleaved pack), and
+hipBLASLt plus swiglu_packed; the fused result is checked equal to the
+two-step one before it is timed.
 
 Run on a GPU box:
   python tools/gemm_decode_bench.py [--check-only]
@@ -84,9 +88,21 @@ def main():
       # mxfp4: no tolerance, the bits of the bf16 kernel on the dequantized weight
       y4 = hip.skinny_gemm_mxfp4(x, wq, ws, 1, N, None)
       assert torch.equal(y4, hip.skinny_gemm_packed(x, wp_dq, N, None)), f"{name} M={M} mxfp4: bits differ"
+      glu_row = name.startswith("gate_up") and hip.skinny_plan_nsplit(N, K) == 1
+      if glu_row:
+        wg = ops.pack_decode_weight_glu(w)
+        two_step = lambda: hip.swiglu_packed(hip.skinny_gemm_packed(x, wp, N, None))
+        fused = lambda: hip.skinny_gemm_packed_glu(x, wg, N)
+        assert torch.equal(fused(), two_step()), f"{name} M={M} fused SwiGLU store: bits differ"
       if args.check_only:
         print(f"{name:<10} {M:>4} ok")
         continue
+      if glu_row:
+        t_two, t_fused = time_us(two_step), time_us(fused)
+        t_lib = time_us(lambda: hip.swiglu_packed(torch.nn.functional.linear(x, w)))
+        print(f"{name:<10} {M:>4} +swiglu: packed {t_two:.1f} us, fused store {t_fused:.1f} us, "
+              f"blaslt {t_lib:.1f} us", flush=True)
+        del wg
       t_bl = time_us(lambda: torch.nn.functional.linear(x, w))
       os.environ["XOT_SKINNY_BN"] = "128"
       t_pk = time_us(lambda: hip.skinny_gemm_packed(x, wp, N, None))

@@ -25,8 +25,8 @@ from xotorch_amd import ops
 
 
 class LayerKV(NamedTuple):
-  k: torch.Tensor
-  v: torch.Tensor
+  k: Optional[torch.Tensor]  # None (with v) in a packed-only cache (ShardKVCache(plain=False))
+  v: Optional[torch.Tensor]
   kp: Optional[torch.Tensor] = None  # MFMA-packed K (cuda, hd 128 or 256; bf16 or e4m3 bytes)
   vp: Optional[torch.Tensor] = None  # MFMA-packed V (same head dims and dtype as kp)
   ksc: Optional[torch.Tensor] = None  # fp8 mode: per-row K scales [B, KVH, T32]
@@ -42,10 +42,15 @@ class ShardKVCache:
 
   def __init__(self, n_layers: int, batch: int, n_kv_heads: int, capacity: int, head_dim: int,
                dtype: torch.dtype = torch.bfloat16, device: str = "cpu",
-               v_dim: Optional[int] = None):
+               v_dim: Optional[int] = None, plain: bool = True):
     """v_dim: per-position width of the v tensor when it differs from
     head_dim (MLA latent caches: k stores the kv_lora latent, v the shared
-    roped key — see ModelConfig.kv_cache_dims())."""
+    roped key — see ModelConfig.kv_cache_dims()).
+    plain=False: a packed-only cache, LayerKV.k / .v are None. For callers
+    whose append and attention read only (kp, vp): the llama decoder with MFMA
+    attention. Honoured only where the bf16 GQA packed copies are allocated
+    and XOT_FP8_KV is off (fp8-KV prefill reads the plain cache); anywhere
+    else the argument is ignored and the plain tensors are allocated."""
     self.capacity = capacity
     self.batch = batch
     self.caches: List[LayerKV] = []
@@ -74,9 +79,13 @@ class ShardKVCache:
     # fp8-KV: e4m3 packed copies (half the decode stream) + per-row scales;
     # the plain cache stays in `dtype` for prefill
     fp8_kv = kp_shape is not None and os.getenv("XOT_FP8_KV", "0") == "1"
+    gqa_packed = kp_shape is not None and len(kp_shape) == 6
+    self.plain = plain or not (gqa_packed and dtype == torch.bfloat16 and not fp8_kv)
     for _ in range(n_layers):
-      layer = [torch.zeros(batch, n_kv_heads, capacity, head_dim, dtype=dtype, device=device),
-               torch.zeros(batch, n_kv_heads, capacity, vd, dtype=dtype, device=device)]
+      layer = [None, None]
+      if self.plain:
+        layer = [torch.zeros(batch, n_kv_heads, capacity, head_dim, dtype=dtype, device=device),
+                 torch.zeros(batch, n_kv_heads, capacity, vd, dtype=dtype, device=device)]
       if kp_shape is not None:
         pdt = torch.uint8 if fp8_kv else dtype
         layer += [torch.zeros(kp_shape, dtype=pdt, device=device),
@@ -87,10 +96,11 @@ class ShardKVCache:
 
   @classmethod
   def for_config(cls, cfg, n_layers: int, batch: int, capacity: int,
-                 dtype: torch.dtype = torch.bfloat16, device: str = "cpu") -> "ShardKVCache":
+                 dtype: torch.dtype = torch.bfloat16, device: str = "cpu",
+                 plain: bool = True) -> "ShardKVCache":
     """The cache `cfg`'s decoder expects (ModelConfig.kv_cache_dims())."""
     heads, k_dim, v_dim = cfg.kv_cache_dims()
-    return cls(n_layers, batch, heads, capacity, k_dim, dtype, device, v_dim=v_dim)
+    return cls(n_layers, batch, heads, capacity, k_dim, dtype, device, v_dim=v_dim, plain=plain)
 
   def rows(self, b0: int, b1: int) -> List[LayerKV]:
     """Every layer's LayerKV.rows(b0, b1): a batch slice of the whole cache."""
@@ -104,16 +114,12 @@ class ShardKVCache:
 
   def reset(self):
     for c in self.caches:
-      c.k.zero_()
-      c.v.zero_()
-      if c.kp is not None:
-        c.kp.zero_()
-        c.vp.zero_()
+      for t in (c.k, c.v, c.kp, c.vp):
+        if t is not None:
+          t.zero_()
 
   def nbytes(self) -> int:
     total = 0
     for c in self.caches:
-      total += c.k.numel() * c.k.element_size() + c.v.numel() * c.v.element_size()
-      if c.kp is not None:
-        total += c.kp.numel() * c.kp.element_size() + c.vp.numel() * c.vp.element_size()
+      total += sum(t.numel() * t.element_size() for t in (c.k, c.v, c.kp, c.vp) if t is not None)
     return total

@@ -17,7 +17,9 @@ from xotorch_amd import ops
 # key -> the route that won when timed in-situ (first eligible call, before
 # hipGraph capture); seed it to force a route. (N, K, M) -> "packed" | "xreg" |
 # "blaslt" for a GEMM, ("w4", N, K, M) -> "mxfp4" | "blaslt" for one in MXFP4
-# mode, ("fuse_swiglu", N, I, M) -> "fused" | "split" for the MLP.
+# mode, ("fuse_swiglu", N, I, M) -> "fused" | "split" for the MLP. For a gate_up
+# with the GLU-interleaved pack, llama.MLP races under the GEMM's (N, K, M):
+# "packed" is the GEMM with SwiGLU in its store, "blaslt" the library + swiglu.
 DECODE_PICKS: dict = {}
 
 
@@ -95,6 +97,12 @@ class XotLinear(nn.Linear):
     self.weight_packed_w4 = None  # MXFP4 code image (ops.pack_decode_weight_mxfp4)
     self.weight_scale_w4 = None   # its e8m0 scale image
     self.keep_bf16 = False  # W4 mode leaves this module's weight and pack in bf16 (lm_head)
+    # glu_store: set by the model's pack policy on a dense gate_up projection
+    # (llama.pack_decode_weights); _pack() then stores the GLU-interleaved image.
+    # glu_packed: weight_packed IS that image, which only
+    # ops.skinny_gemm_packed_glu reads (llama.MLP.forward), never _gemm
+    self.glu_store = False
+    self.glu_packed = False
     self._w8 = None  # lazily cached fp8 prefill copy (_fp8_prefill)
     self._w8_scale = None
 
@@ -120,10 +128,15 @@ class XotLinear(nn.Linear):
         with torch.no_grad():
           self.weight.copy_(w_dq)
     elif self.weight_packed is None:
-      self.weight_packed = ops.pack_decode_weight(self.weight.detach())
+      if self.glu_store:
+        self.weight_packed = ops.pack_decode_weight_glu(self.weight.detach())
+        self.glu_packed = True
+      else:
+        self.weight_packed = ops.pack_decode_weight(self.weight.detach())
 
   def unpack_decode(self):
     self.weight_packed = None
+    self.glu_packed = False
     self.weight_packed_fp8 = None
     self.weight_packed_w4 = None
     self.weight_scale_w4 = None
@@ -193,7 +206,7 @@ class XotLinear(nn.Linear):
           if epilogue is not None:
             return ops.skinny_gemm_mxfp4_epilogue(x, wq, ws, N, b, epilogue)
           return ops.skinny_gemm_mxfp4(x, wq, ws, 1, N, b)
-      if M and wp is not None:
+      if M and wp is not None and not self.glu_packed:  # a GLU-interleaved pack goes to the library here
         b = self.bias
         use = auto_pick((N, K, M), "gemm", "NKM", 0.95, lambda: [
           ("blaslt", lambda: torch.nn.functional.linear(x, self.weight, b)),

@@ -116,8 +116,22 @@ class MLP(nn.Module):
 
   def forward(self, x, epilogue=None):
     """epilogue: see XotLinear.forward — the down projection carries it."""
-    gu = self.gate_up_proj(x)
     dp, I = self.down_proj, self.intermediate
+    gup = self.gate_up_proj
+    if getattr(gup, "glu_packed", False):
+      # GLU-interleaved pack: the gate_up GEMM applies SwiGLU in its store and
+      # no [.., 2I] tensor exists, so the down-side fuse_swiglu race has nothing
+      # to fuse. Raced under the GEMM's own key against the library + swiglu.
+      N2, K = gup.weight.shape
+      M = decode_rows(x, K)
+      two_step = lambda: ops.swiglu_packed(gup(x))  # XotLinear sends this pack to the library
+      if M:
+        use = auto_pick((N2, K, M), "gemm+swiglu", "NKM", 0.95, lambda: [
+          ("blaslt", two_step),
+          ("packed", lambda: ops.skinny_gemm_packed_glu(x, gup.weight_packed, N2))])
+      h = ops.skinny_gemm_packed_glu(x, gup.weight_packed, N2) if M and use == "packed" else two_step()
+      return dp(h) if epilogue is None else dp(h, epilogue)
+    gu = gup(x)
     wp = getattr(dp, "weight_packed", None)  # dp may be a LoRA wrapper (train/lora.py)
     if wp is not None and os.getenv("XOT_FUSE_SWIGLU", "1") == "1":
       M = decode_rows(gu, 2 * I)
@@ -282,6 +296,22 @@ def pack_group_partial(grp, bytes_per: int, reserve_bytes: int, free_bytes) -> i
   return n
 
 
+def glu_store_module(model, name: str, mod: XotLinear, fmt: str) -> bool:
+  """Whether the gate_up projection `name` gets the GLU-interleaved pack
+  (SwiGLU in the GEMM's store, MLP.forward): the gate_up_proj of a dense
+  llama MLP (not an expert, not gemma2's GeGLU or DeepSeek's MLP, which are
+  other classes), bf16 format, no bias, and a shape the packed kernel's
+  ordinary plan does not split along K, so the fused launch, which never
+  splits, has that plan's bits. XOT_GLU_STORE=0 flags none."""
+  if fmt != "bf16" or not ops.glu_store_enabled() or "experts." in name or mod.bias is not None:
+    return False
+  parent, _, leaf = name.rpartition(".")
+  if leaf != "gate_up_proj" or type(model.get_submodule(parent)) is not MLP:
+    return False
+  N, K = mod.weight.shape
+  return N % 128 == 0 and K % 64 == 0 and ops.skinny_plan_nsplit(N, K) == 1
+
+
 def pack_decode_weights(model, reserve_bytes: int) -> int:
   """Prepack decode-GEMM weights (second copy in MFMA fragment order) in
   descending measured-win order — down_proj (hipBLASLt ~3 TB/s at K=28672
@@ -312,6 +342,7 @@ def pack_decode_weights(model, reserve_bytes: int) -> int:
       groups[1].append(mod)
     elif "gate_up_proj" in name:
       groups[2].append(mod)
+      mod.glu_store = glu_store_module(model, name, mod, fmt)
     else:  # qkv_proj / o_proj / experts' projections
       groups[3].append(mod)
   if mode != "all" and fmt == "bf16":

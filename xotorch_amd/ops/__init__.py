@@ -111,6 +111,15 @@ def gqa_packed_kv(head_dim: int, dtype: torch.dtype) -> bool:
   return head_dim in PACKED_HEAD_DIMS and dtype == torch.bfloat16 and mfma_attn_enabled()
 
 
+def _need_plain_cache(op: str, k_cache, why: str):
+  """A packed-only KV cache (ShardKVCache(plain=False)) has no [B, KVH, T, hd]
+  tensors: a route that reads them is an error, never a silent fallback."""
+  if k_cache is None:
+    raise RuntimeError(
+      f"{op}: this call needs the plain KV cache, but the cache was built without it "
+      f"(plain=False): {why}. Build the cache with plain=True (XOT_KV_PLAIN=1 on the ring path).")
+
+
 def rope_apply(q, k, cos, sin, positions):
   """Standalone RoPE (training / oracle paths). On the GPU inference hot
   path RoPE is fused into rope_qkv_append — there is deliberately no
@@ -127,9 +136,11 @@ def rope_qkv_append(qkv, cos, sin, positions, k_cache, v_cache, n_heads: int, n_
   cache copies (kp, vp) exist they are appended too.
   """
   if _use_hip(qkv) and qkv.dtype == torch.bfloat16:
+    # k_cache / v_cache None: a packed-only cache, the kernel skips the plain stores
     _hip.rope_qkv_append(qkv, cos, sin, positions, k_cache, v_cache, n_heads, n_kv_heads, head_dim,
                          kp, vp, q_norm, k_norm, norm_eps, k_scale, v_scale)
     return
+  _need_plain_cache("rope_qkv_append", k_cache, "the torch path appends to the plain cache")
   torch_ref.rope_qkv_append(qkv, cos, sin, positions, k_cache, v_cache, n_heads, n_kv_heads,
                             head_dim, q_norm, k_norm, norm_eps)
 
@@ -142,6 +153,9 @@ def attn_prefill(q, k_cache, v_cache, start_pos: int, s_len: int, kp=None, vp=No
     # softcap/window run gemma2 semantics inside the same kernel (fp8-KV
     # mode keeps prefill on the plain bf16 cache via the sdpa path below)
     return _hip.attn_prefill_mfma(q, kp, vp, start_pos, scale or 0.0, softcap, window)
+  _need_plain_cache("attn_prefill", k_cache,
+                    "only the MFMA prefill kernel (XOT_MFMA_ATTN=1, bf16 packed copies, head_dim 128 or 256) "
+                    "reads the packed copies")
   if q.is_cuda and not softcap and not window:
     # fallback: sdpa (rocm flash/mem-efficient backends) in model dtype with
     # native GQA — hd outside PACKED_HEAD_DIMS or unpacked-cache path
@@ -170,12 +184,18 @@ def attn_decode(q, k_cache, v_cache, seq_len, kp=None, vp=None,
   if _use_hip(q) and q.dtype == torch.bfloat16:
     if not isinstance(seq_len, torch.Tensor):
       seq_len = torch.full((q.shape[0],), int(seq_len), dtype=torch.int32, device=q.device)
-    rep = q.shape[2] // k_cache.shape[1]
+    # a packed-only cache (k_cache None): kv heads and capacity from kp [B, KVH, T32/16, ..]
+    kvh, cap = (k_cache.shape[1], k_cache.shape[2]) if k_cache is not None else (kp.shape[1], kp.shape[2] * 16)
+    rep = q.shape[2] // kvh
     if kp is not None and rep <= 16 and mfma_attn_enabled():
-      return _hip.attn_decode_mfma(q, kp, vp, seq_len, k_cache.shape[2],
+      return _hip.attn_decode_mfma(q, kp, vp, seq_len, cap,
                                    scale or 0.0, softcap, window, k_scale, v_scale)
+    _need_plain_cache("attn_decode", k_cache,
+                      "only the MFMA decode kernel (XOT_MFMA_ATTN=1, at most 16 query heads per kv head) "
+                      "reads the packed copies")
     if not softcap and not window and scale is None:
       return _hip.attn_decode(q, k_cache, v_cache, seq_len)
+  _need_plain_cache("attn_decode", k_cache, "the torch path reads the plain cache")
   return torch_ref.attn_decode(q, k_cache, v_cache, seq_len, scale, softcap, window)
 
 
@@ -216,6 +236,9 @@ def _binding(name: str):
 
 skinny_gemm_packed = _binding("skinny_gemm_packed")                # (x, wp, N, bias) -> [.., N]
 skinny_gemm_packed_xreg = _binding("skinny_gemm_packed_xreg")      # the same, x held in registers
+# (x, wp from pack_decode_weight_glu, N = 2I) -> silu(gate) * up [.., I]: SwiGLU in the store, never split-K
+skinny_gemm_packed_glu = _binding("skinny_gemm_packed_glu")
+skinny_plan_nsplit = _binding("skinny_plan_nsplit")  # (N, K) -> K splits of the packed kernel's ordinary plan
 skinny_gemm_packed_swiglu = _binding("skinny_gemm_packed_swiglu")  # (gu [.., 2I], wp, N, bias): swiglu + GEMM
 skinny_gemm_grouped = _binding("skinny_gemm_grouped")  # (x [E, C, K], stacked wp, E, N) -> [E, C, N]
 quant_fp8_rows = _binding("quant_fp8_rows")            # (x [M, K]) -> (e4m3 bytes [M, K], fp32 row scales [M])
@@ -264,6 +287,39 @@ def pack_decode_weight(w: torch.Tensor) -> torch.Tensor:
   N, K = w.shape
   assert N % 32 == 0 and K % 64 == 0, (N, K)
   return w.view(N // 32, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
+
+
+def glu_store_enabled() -> bool:
+  """XOT_GLU_STORE (default 1, read at pack time): dense llama gate_up
+  projections get the GLU-interleaved pack and run SwiGLU in the GEMM's store;
+  0 keeps the plain pack and the separate swiglu_packed launch."""
+  return os.getenv("XOT_GLU_STORE", "1") != "0"
+
+
+def glu_interleave_perm(I: int) -> torch.Tensor:
+  """Row order of the GLU-interleaved pack of a fused [gate; up] weight
+  [2I, K] (gate rows 0..I-1, up rows I..2I-1): perm[r] = the weight row that
+  packed row r holds. With n32 = r // 32, p = (r % 32) // 16, w = r % 16 and
+  c = 16 * n32 + 8 * p + w % 8, row r is gate row c when w < 8, else up row c
+  (= row I + c). In the 32x32 MFMA D layout a lane owns rows w and w + 8 of
+  each 16-row half of a tile, so it holds both halves of its SwiGLU pairs."""
+  assert I % 64 == 0, I  # 2I % 128 == 0, the packed kernel's rule
+  r = torch.arange(2 * I)
+  w = r % 16
+  c = 16 * (r // 32) + 8 * ((r % 32) // 16) + w % 8
+  return torch.where(w < 8, c, I + c)
+
+
+def pack_decode_weight_glu(w: torch.Tensor) -> torch.Tensor:
+  """pack_decode_weight(w[glu_interleave_perm(I)]) of a fused [gate; up]
+  weight [2I, K], for skinny_gemm_packed_glu. One strided copy, without the
+  row-gathered temporary: the permutation is a transpose of the row index
+  read as [half, n32, p, w % 8] into [n32, p, half, w % 8]."""
+  N, K = w.shape
+  I = N // 2
+  assert N % 128 == 0 and K % 64 == 0, (N, K)
+  v = w.view(2, I // 16, 2, 8, K // 16, 2, 8)  # [half, n32, p, w8, k16, k-half, 8]
+  return v.permute(1, 4, 5, 2, 0, 3, 6).reshape(N // 32, K // 16, 2, 32, 8).contiguous()
 
 
 def pack_decode_weight_fp8(w: torch.Tensor):

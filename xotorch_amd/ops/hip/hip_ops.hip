@@ -298,15 +298,18 @@ __global__ __launch_bounds__(256) void rope_qkv_append_kernel(
     float f1[PAIRS], f2[PAIRS];
     rope_head_pair(row, kn, cosb, sinb, pos, hd, lane, norm_eps, f1, f2);
     const size_t ktile = (head * (T32 >> 4) + (pos >> 4)) * GQA_KTILE(hd);
-    unsigned short* dst = kc + (head * T + pos) * hd;
+    // kc / vc null: a packed-only cache, there is no plain copy to write
+    unsigned short* dst = kc ? kc + (head * T + pos) * hd : nullptr;
     float mx = 0.f;
 #pragma unroll
     for (int e = 0; e < PAIRS; ++e) {
       const int p = lane + e * 64;
       mx = fmaxf(mx, fmaxf(fabsf(f1[e]), fabsf(f2[e])));
       if (p < hd2) {
-        dst[p] = f2b(f1[e]);
-        dst[p + hd2] = f2b(f2[e]);
+        if (dst) {
+          dst[p] = f2b(f1[e]);
+          dst[p + hd2] = f2b(f2[e]);
+        }
         if (kpc) {
           kpc[ktile + kfrag_off(p, pos)] = f2b(f1[e]);
           kpc[ktile + kfrag_off(p + hd2, pos)] = f2b(f2[e]);
@@ -328,14 +331,14 @@ __global__ __launch_bounds__(256) void rope_qkv_append_kernel(
     }
   } else {
     const size_t head = (size_t)(b * KVH + (slot - H - KVH));
-    unsigned short* dst = vc + (head * T + pos) * hd;
+    unsigned short* dst = vc ? vc + (head * T + pos) * hd : nullptr;
     const size_t vhead = head * GQA_VGROUPS(hd) * (T32 >> 5) * FRAG;
     float mx = 0.f;
 #pragma unroll
     for (int e = 0; e < PAIRS; ++e) {
       const int d = e * 128 + lane * 2;
       if (d < hd) {
-        *(unsigned int*)(dst + d) = *(const unsigned int*)(row + d);
+        if (dst) *(unsigned int*)(dst + d) = *(const unsigned int*)(row + d);
         mx = fmaxf(mx, fmaxf(fabsf(b2f(row[d])), fabsf(b2f(row[d + 1]))));
         if (vpc) {
 #pragma unroll
@@ -1686,6 +1689,16 @@ __global__ __launch_bounds__(256) void attn_decode_mla_kernel(
 // SwiGLU: silu(gate) * up, elementwise, vectorized
 // ---------------------------------------------------------------------------
 
+// The one SwiGLU expression: silu(gate) * up on bf16 bits, fp32 math, one
+// rounding. Every kernel that applies the activation calls this, so the
+// elementwise kernels, the down GEMM's X staging and the gate_up GEMM's fused
+// store give the same bits.
+DEVINL unsigned short swiglu_bf16(unsigned short g, unsigned short u) {
+  const float gf = b2f(g);
+  const float s = gf * __builtin_amdgcn_rcpf(1.f + __expf(-gf));
+  return f2b(s * b2f(u));
+}
+
 __global__ __launch_bounds__(256) void swiglu_kernel(
     const unsigned short* __restrict__ g, const unsigned short* __restrict__ u,
     unsigned short* __restrict__ out, long long n8) {
@@ -1695,11 +1708,7 @@ __global__ __launch_bounds__(256) void swiglu_kernel(
     ushort8 uv = *(const ushort8*)(u + i * 8);
     ushort8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gf = b2f(gv[j]);
-      const float s = gf * __builtin_amdgcn_rcpf(1.f + __expf(-gf));
-      o[j] = f2b(s * b2f(uv[j]));
-    }
+    for (int j = 0; j < 8; ++j) o[j] = swiglu_bf16(gv[j], uv[j]);
     *(ushort8*)(out + i * 8) = o;
   }
 }
@@ -1719,11 +1728,7 @@ __global__ __launch_bounds__(256) void swiglu_packed_kernel(
     ushort8 uv = *(const ushort8*)(base + I);
     ushort8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gf = b2f(gv[j]);
-      const float s = gf * __builtin_amdgcn_rcpf(1.f + __expf(-gf));
-      o[j] = f2b(s * b2f(uv[j]));
-    }
+    for (int j = 0; j < 8; ++j) o[j] = swiglu_bf16(gv[j], uv[j]);
     *(ushort8*)(out + i * 8) = o;
   }
 }
@@ -1788,7 +1793,14 @@ DEVINL bf16x8 load_bf16x8(const unsigned short* p) {
 // P [nsplit, rows_total, N] (bias is added by the combine), otherwise bf16
 // + bias into Y. SCALED (fp8) dequantizes by sx[m] * sw[sw_base + n]
 // (sw_base = the expert's offset into sw); the bf16 kernels pass no scales.
-template <int MT, bool SPLIT, bool SCALED = false>
+// GLU (unsplit bf16, no bias): the weight rows are in the GLU-interleaved order
+// of ops.glu_interleave_perm, so in every 32-row tile n_local w and w + 8
+// (w % 16 < 8) are the gate and up row of one SwiGLU column and a lane's
+// accumulators 8p + j and 8p + 4 + j are such a pair. Both sums are rounded to
+// bf16 as the plain store rounds them, then swiglu_bf16 gives what
+// swiglu_packed gives on the plain output: Y is [rows, N / 2], the lane's 4
+// results of half p go to columns 16 * n32 + 8 * p + 4 * (lane >> 5) + j.
+template <int MT, bool SPLIT, bool SCALED = false, bool GLU = false>
 DEVINL void skinny_store_acc(const floatx16 (&acc)[MT], unsigned short* Y, float* P,
                              const unsigned short* bias, int N, int split, int rows_total,
                              int m0, int nbase, const float* sx = nullptr,
@@ -1798,7 +1810,20 @@ DEVINL void skinny_store_acc(const floatx16 (&acc)[MT], unsigned short* Y, float
     const int m = m0 + t * 32;
     float sxm = 1.f;
     if (SCALED) sxm = sx[m];
-    if (SPLIT) {
+    if constexpr (GLU) {
+      static_assert(!SPLIT && !SCALED, "the GLU store takes final bf16 sums");
+      const int I = N >> 1;
+      unsigned short* yrow = Y + (size_t)m * I + ((nbase >> 5) << 4) + (nbase & 31);
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        unsigned short o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          o[j] = swiglu_bf16(f2b(acc[t][8 * p + j]), f2b(acc[t][8 * p + 4 + j]));
+        *reinterpret_cast<unsigned long long*>(yrow + 8 * p) =
+            *reinterpret_cast<unsigned long long*>(o);
+      }
+    } else if (SPLIT) {
       float* prow = P + ((size_t)split * rows_total + m) * N;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -1908,10 +1933,7 @@ DEVINL ushort8 skinny_stage_load(const unsigned short* p, long long K) {
   if (SWIGLU) {
     const ushort8 up = *(const ushort8*)(p + K);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float g = b2f(v[j]);
-      v[j] = f2b(g * __builtin_amdgcn_rcpf(1.f + __expf(-g)) * b2f(up[j]));
-    }
+    for (int j = 0; j < 8; ++j) v[j] = swiglu_bf16(v[j], up[j]);
   }
   return v;
 }
@@ -1967,7 +1989,11 @@ DEVINL bf16x8 w4_frag(unsigned int q, float scale) {
 // e8m0 byte -> fp32 2^(e8 - 127); the pack keeps e8 in [2, 252], a normal fp32
 DEVINL float e8m0_scale(unsigned int e8) { return __uint_as_float(e8 << 23); }
 
-template <int MT, bool SPLIT, int BK, bool SWIGLU = false, int NW = 4, bool W4 = false>
+//
+// GLU = the SwiGLU store of the gate_up projection (skinny_store_acc): Wp is
+// the GLU-interleaved pack and Y is [rows, N / 2]. Nothing before the store
+// changes. Instantiated for SPLIT = SWIGLU = W4 = false only.
+template <int MT, bool SPLIT, int BK, bool SWIGLU = false, int NW = 4, bool W4 = false, bool GLU = false>
 __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(
     const unsigned short* __restrict__ Wp, const unsigned short* __restrict__ X,
     unsigned short* __restrict__ Y, float* __restrict__ P,
@@ -2138,12 +2164,22 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(
     }                                                                                          \
     SGP_STEP_TAIL((BUF) & 1)                                                                   \
   }
-  // staging tail of a step that read LDS image BUF: fill the image of step s+1
+  // staging tail of a step that read LDS image BUF: fill the image of step s+1.
+  // GLU, last step: the branch around this tail goes from the step's last MFMA
+  // to the store, and on that taken edge the compiler pads the MFMA-write ->
+  // accumulator-read wait states for the fall-through path only. The GLU store
+  // reads acc[15] first; at MT = 1 that read came 7 states after the MFMA and
+  // returned the sum without the last k-chunk (measured: every output that uses
+  // it, whenever the last step is the odd one after the loop). The nops sit on
+  // that edge, ahead of the register copies the store begins with: 20 states
+  // cover the longest MFMA. The other instances are compiled as before.
 #define SGP_STEP_TAIL(BUF)                                                                   \
     if (!last) {                                                                               \
       if (XBUFS == 1) __syncthreads();                                                         \
       SGP_XSTORE(XBUFS == 2 ? 1 - (BUF) : 0)                                                   \
       __syncthreads();                                                                         \
+    } else if (GLU) {                                                                          \
+      asm volatile("s_nop 9\n\ts_nop 9");                                                      \
     }
 
   int s = 0;
@@ -2176,9 +2212,9 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(
 #undef SGP_XSTORE
 
   // rows_total spans all experts
-  skinny_store_acc<MT, SPLIT>(acc, Y, P, bias, N, split, gridDim.y * MT * 32,
-                              e * MT * 32 + (lane & 31),
-                              tile * (NW * 32) + wv * 32 + 4 * (lane >> 5));
+  skinny_store_acc<MT, SPLIT, false, GLU>(acc, Y, P, bias, N, split, gridDim.y * MT * 32,
+                                          e * MT * 32 + (lane & 31),
+                                          tile * (NW * 32) + wv * 32 + 4 * (lane >> 5));
 }
 
 // ---------------------------------------------------------------------------
@@ -2628,12 +2664,11 @@ static float* fp8_scale_ptr(const c10::optional<torch::Tensor>& s) {
 // reaches ~1.5 blocks/CU (384 on MI355X's 256 CUs), splitting K only adds
 // partial-write + combine overhead (measured: gate_up 448 tiles 176 -> 162 us
 // unsplit); below it, split K until ~2 blocks/CU. Overridable for tuning.
+// Read per call, like XOT_SKINNY_BK64 and XOT_SKINNY_BN: the equality tests of
+// the unsplit GLU launch set it to get an unsplit plain plan to compare with.
 static int skinny_target_blocks() {
-  static int t = [] {
-    const char* e = getenv("XOT_SKINNY_TARGET");
-    return e ? atoi(e) : 384;
-  }();
-  return t;
+  const char* e = getenv("XOT_SKINNY_TARGET");
+  return e ? atoi(e) : 384;
 }
 
 torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor w, double eps, double w_bias) {
@@ -2665,18 +2700,22 @@ std::vector<torch::Tensor> rmsnorm_residual(torch::Tensor x, torch::Tensor res, 
 }
 
 void rope_qkv_append(torch::Tensor qkv, torch::Tensor cos, torch::Tensor sin,
-                     torch::Tensor positions, torch::Tensor kc, torch::Tensor vc,
-                     int64_t n_heads, int64_t n_kv_heads, int64_t head_dim,
+                     torch::Tensor positions, c10::optional<torch::Tensor> kc,
+                     c10::optional<torch::Tensor> vc, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim,
                      c10::optional<torch::Tensor> kp, c10::optional<torch::Tensor> vp,
                      c10::optional<torch::Tensor> q_norm, c10::optional<torch::Tensor> k_norm,
                      double norm_eps,
                      c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale) {
   CHK(qkv.is_cuda() && qkv.dtype() == torch::kBFloat16 && qkv.is_contiguous());
-  CHK(kc.is_contiguous() && vc.is_contiguous());
+  // kc / vc absent: a packed-only cache (kp / vp required), T is then T32
+  const bool plain = kc.has_value();
+  CHK(plain == vc.has_value());
+  if (plain) CHK(kc->is_contiguous() && vc->is_contiguous());
+  TORCH_CHECK(plain || (kp.has_value() && vp.has_value()),
+              "rope_qkv_append: no plain cache and no packed copies to append to");
   CHK(positions.dtype() == torch::kInt32 && positions.is_cuda());
   const int B = qkv.size(0), S = qkv.size(1);
   const int H = (int)n_heads, KVH = (int)n_kv_heads, hd = (int)head_dim;
-  const int T = kc.size(2);
   CHK(qkv.size(2) == (H + 2 * KVH) * hd);
   CHK(hd <= 256 && hd % 2 == 0);
   const int npos = (int)positions.numel();
@@ -2696,6 +2735,7 @@ void rope_qkv_append(torch::Tensor qkv, torch::Tensor cos, torch::Tensor sin,
       svp = fp8_scale_ptr(v_scale);
     }
   }
+  const int T = plain ? (int)kc->size(2) : T32;
   const unsigned short* qnp = nullptr;
   const unsigned short* knp = nullptr;
   if (q_norm.has_value()) {
@@ -2713,8 +2753,9 @@ void rope_qkv_append(torch::Tensor qkv, torch::Tensor cos, torch::Tensor sin,
     hipLaunchKernelGGL((rope_qkv_append_kernel<decltype(wide)::value ? 2 : 1>), dim3(blocks), dim3(256), 0,
                        cur_stream(),
                        (unsigned short*)qkv.data_ptr(), cos.data_ptr<float>(), sin.data_ptr<float>(),
-                       positions.data_ptr<int>(), (unsigned short*)kc.data_ptr(),
-                       (unsigned short*)vc.data_ptr(), B, S, H, KVH, hd, T, pc.kp, pc.vp, T32,
+                       positions.data_ptr<int>(),
+                       plain ? (unsigned short*)kc->data_ptr() : nullptr,
+                       plain ? (unsigned short*)vc->data_ptr() : nullptr, B, S, H, KVH, hd, T, pc.kp, pc.vp, T32,
                        qnp, knp, (float)norm_eps, npos, pc.kp8, pc.vp8, skp, svp);
   });
 }
@@ -3124,12 +3165,15 @@ struct SkinnyPlan {
 };
 
 // E = experts sharing the launch (grid.y); k_align = 16 for the unpacked v1
-// kernel, 64 for everything on the prepack.
-static SkinnyPlan skinny_plan(long long N, long long K, long long E, int k_align, bool has_bk128) {
+// kernel, 64 for everything on the prepack. unsplit = never split K (the GLU
+// store needs final sums); the BK rule then applies to kc = K.
+static SkinnyPlan skinny_plan(long long N, long long K, long long E, int k_align, bool has_bk128,
+                              bool unsplit = false) {
   const int ntiles = (int)(N / 128);
   // oversubscribe the 256 CUs (>=2 blocks/CU) while keeping K/SPLITK >= ~1024
   int nsplit = 1;
-  while (ntiles * nsplit * E < skinny_target_blocks() && (K / (nsplit * 2)) >= 1024 && nsplit < 16) nsplit *= 2;
+  const int target = unsplit ? 0 : skinny_target_blocks();
+  while (ntiles * nsplit * E < target && (K / (nsplit * 2)) >= 1024 && nsplit < 16) nsplit *= 2;
   const int kc = (int)((K / nsplit + k_align - 1) / k_align * k_align);
   while ((long long)kc * (nsplit - 1) >= K) nsplit--;  // drop empty splits
   // BK=128 halves the staging-barrier count per byte; needs 128-aligned
@@ -3216,18 +3260,19 @@ static bool skinny_wide_tile(long long rows, long long N, long long E, const Ski
 // and the wide tile only halves grid.x, so P and the combine do not change.
 // With an epilogue the row kernel takes the combine's place (split) or
 // follows the GEMM's bf16 y (unsplit); its results are left in *epi and the
-// returned y is undefined when split.
+// returned y is undefined when split. unsplit = plan without split-K (the
+// GLU launcher, whose ysizes end in N / 2).
 template <bool PACKED, class F>
 static torch::Tensor skinny_run(const torch::Tensor& x, at::IntArrayRef ysizes, long long rows,
                                 long long N, long long K, long long E,
                                 const c10::optional<torch::Tensor>& bias, int k_align, F&& launch,
-                                SkinnyEpilogue* epi = nullptr) {
+                                SkinnyEpilogue* epi = nullptr, bool unsplit = false) {
   const unsigned short* bptr = nullptr;
   if (bias.has_value()) {
     CHK(bias->is_contiguous() && bias->dtype() == torch::kBFloat16 && bias->numel() == N);
     bptr = (const unsigned short*)bias->data_ptr();
   }
-  const SkinnyPlan p = skinny_plan(N, K, E, k_align, PACKED);
+  const SkinnyPlan p = skinny_plan(N, K, E, k_align, PACKED, unsplit);
   const bool is_split = p.nsplit > 1;
   const bool wide = PACKED && skinny_wide_tile(rows, N, E, p);
   torch::Tensor y;
@@ -3316,6 +3361,41 @@ static torch::Tensor skinny_gemm_packed_impl(const torch::Tensor& x, const torch
 torch::Tensor skinny_gemm_packed(torch::Tensor x, torch::Tensor wp, int64_t N,
                                  c10::optional<torch::Tensor> bias) {
   return skinny_gemm_packed_impl(x, wp, N, bias, nullptr);
+}
+
+// gate_up projection with the SwiGLU in its store: wp is the GLU-interleaved
+// pack (ops.pack_decode_weight_glu) of the fused [gate; up] weight [N, K],
+// N = 2I; returns silu(x @ gate^T) * (x @ up^T) as [.., N / 2], the bits of
+// swiglu_packed(skinny_gemm_packed(x, plain pack)) where that plan is unsplit.
+// Always unsplit; BK and the tile follow the usual rules for that plan.
+torch::Tensor skinny_gemm_packed_glu(torch::Tensor x, torch::Tensor wp, int64_t N) {
+  CHK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.is_contiguous());
+  CHK(wp.is_cuda() && wp.dtype() == torch::kBFloat16 && wp.is_contiguous());
+  const long long K = wp.numel() / N;
+  const long long M = x.numel() / K;
+  CHK(M >= 32 && M <= 256 && M % 32 == 0);
+  CHK(N % 128 == 0 && K % 64 == 0 && x.size(-1) == K);
+  auto sizes = x.sizes().vec();
+  sizes.back() = (long)(N / 2);
+  return skinny_run<true>(x, sizes, M, N, K, 1, c10::nullopt, 64,
+                          [&](auto mt, auto split, auto bk, auto nw, const SkinnyLaunch& L) {
+    if constexpr (!split.value) {
+      CHK(L.bias == nullptr && L.nsplit == 1 && L.kc == K);
+      hipLaunchKernelGGL((skinny_gemm_packed_kernel<mt.value, false, bk.value, false, nw.value, false, true>),
+                         L.grid, dim3(nw.value * 64), 0, L.stream,
+                         (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(),
+                         L.Y, L.P, L.bias, (int)N, K, L.kc, L.nsplit);
+    } else {
+      TORCH_CHECK(false, "skinny_gemm_packed_glu: the plan must not split K");
+    }
+  }, nullptr, /*unsplit=*/true);
+}
+
+// K splits of the packed kernel's ordinary plan for a [N, K] weight (the
+// model's pack policy asks: the GLU store is for unsplit shapes only)
+int64_t skinny_plan_nsplit(int64_t N, int64_t K) {
+  CHK(N >= 128 && N % 128 == 0 && K % 64 == 0);
+  return skinny_plan(N, K, 1, 64, true).nsplit;
 }
 
 // skinny_gemm_packed + row epilogue: returns {h' = y + res} or, with a norm
@@ -3525,6 +3605,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_packed", &skinny_gemm_packed,
         "decode GEMM on prepacked weights (MFMA fragment order)",
         py::arg("x"), py::arg("wp"), py::arg("n"), py::arg("bias") = py::none());
+  m.def("skinny_gemm_packed_glu", &skinny_gemm_packed_glu,
+        "gate_up decode GEMM on the GLU-interleaved prepack with SwiGLU in the store -> [.., n / 2]",
+        py::arg("x"), py::arg("wp"), py::arg("n"));
+  m.def("skinny_plan_nsplit", &skinny_plan_nsplit,
+        "K splits of the packed decode GEMM's plan for a [n, k] weight", py::arg("n"), py::arg("k"));
   m.def("skinny_gemm_packed_epilogue", &skinny_gemm_packed_epilogue,
         "skinny_gemm_packed + fused combine / residual add / following RMSNorm -> [h', normed]",
         py::arg("x"), py::arg("wp"), py::arg("n"), py::arg("bias"), py::arg("res"),

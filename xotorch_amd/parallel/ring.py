@@ -28,6 +28,7 @@ from xotorch_amd import ops
 from xotorch_amd.engine.kvcache import ShardKVCache
 from xotorch_amd.models.build import build_shard_model
 from xotorch_amd.models.config import ModelConfig, config_from_hf
+from xotorch_amd.models.llama import ShardedModel as LlamaShardedModel
 from xotorch_amd.models.registry import builtin_config
 from xotorch_amd.parallel.comm import RingComm
 from xotorch_amd.parallel.partitioning import Partition, map_partitions_to_shards
@@ -97,15 +98,24 @@ class RingPipeline:
     self.comm = RingComm(device)
 
     self.model = model = build_shard_model(self.cfg, self.shard, dtype, device, seed=seed, fast_init=True)
+    # The llama decoder with MFMA attention appends to and reads only the packed
+    # cache copies, so its caches are built without the plain [B, KVH, T, hd]
+    # tensors (XOT_KV_PLAIN=1 keeps them). ShardKVCache ignores plain=False where
+    # it allocates no bf16 GQA packed copies (CPU, XOT_MFMA_ATTN=0, fp8-KV, ..).
+    packed_only = (isinstance(model, LlamaShardedModel) and self.cfg.n_heads // self.cfg.n_kv_heads <= 16
+                   and os.getenv("XOT_KV_PLAIN", "0") != "1")
+    self.kv_plain = not (packed_only and device == "cuda" and ops.gqa_packed_kv(self.cfg.head_dim, dtype)
+                         and os.getenv("XOT_FP8_KV", "0") != "1")
     if device == "cuda":
       # decode-GEMM weight prepack (memory permitting; KV caches below still
       # need room — reserve their size + headroom before packing greedily)
-      kv_bytes = (
-        self.M * 2 * shards[rank].get_layer_count() * mb_batch * self.cfg.n_kv_heads
-        * self.total_len * self.cfg.head_dim * (2 if dtype == torch.bfloat16 else 4)
-      )
+      per_pos = (self.M * 2 * shards[rank].get_layer_count() * mb_batch * self.cfg.n_kv_heads
+                 * self.cfg.head_dim * (2 if dtype == torch.bfloat16 else 4))
+      kv_bytes = per_pos * self.total_len if self.kv_plain else 0
       if ops.gqa_packed_kv(self.cfg.head_dim, dtype):
-        kv_bytes *= 2  # the MFMA-packed cache copies double KV residency
+        # the MFMA-packed cache copies, at the capacity rounded up to 32: a
+        # second residency beside the plain tensors, the only one without them
+        kv_bytes += per_pos * ((self.total_len + 31) // 32 * 32)
       torch.cuda.empty_cache()  # release init-time cached blocks so the
       # pack policy's mem_get_info reflects actually-usable HBM
       model.pack_decode_weights(reserve_bytes=kv_bytes + (24 << 30))
@@ -113,7 +123,8 @@ class RingPipeline:
     # --- per-micro-batch state ---
     B = mb_batch
     self.caches = [
-      ShardKVCache.for_config(self.cfg, self.shard.get_layer_count(), B, self.total_len, dtype, device)
+      ShardKVCache.for_config(self.cfg, self.shard.get_layer_count(), B, self.total_len, dtype, device,
+                              plain=self.kv_plain)
       for _ in range(self.M)
     ]
     self.positions = [torch.zeros(1, dtype=torch.int32, device=device) for _ in range(self.M)]
