@@ -2165,20 +2165,24 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(
     SGP_STEP_TAIL((BUF) & 1)                                                                   \
   }
   // staging tail of a step that read LDS image BUF: fill the image of step s+1.
-  // GLU, last step: the branch around this tail goes from the step's last MFMA
-  // to the store, and on that taken edge the compiler pads the MFMA-write ->
-  // accumulator-read wait states for the fall-through path only. The GLU store
-  // reads acc[15] first; at MT = 1 that read came 7 states after the MFMA and
-  // returned the sum without the last k-chunk (measured: every output that uses
-  // it, whenever the last step is the odd one after the loop). The nops sit on
-  // that edge, ahead of the register copies the store begins with: 20 states
-  // cover the longest MFMA. The other instances are compiled as before.
+  // Last step: the branch around this tail goes from the step's last MFMA to
+  // the store, and on that taken edge the compiler pads the MFMA-write ->
+  // accumulator-read wait states for the fall-through path only. A store whose
+  // first read is acc[15] of the last m-tile then gets the sum without the last
+  // k-chunk whenever the last step is the odd one after the loop. Measured on
+  // the GLU store at MT = 1 (the read came 7 states after the MFMA) and, by the
+  // integer oracle (docs/KERNELS.md, Accuracy), on the unsplit bf16 store with a
+  // bias at BK = 128, K = 2176: MT 1, 3, 4, 5, with and without the SwiGLU
+  // staging. Which instances the scheduler leaves exposed is not ours to know,
+  // so every instance carries the nops on that edge, ahead of the register
+  // copies the store begins with: 20 states cover the longest MFMA, once per
+  // workgroup.
 #define SGP_STEP_TAIL(BUF)                                                                   \
     if (!last) {                                                                               \
       if (XBUFS == 1) __syncthreads();                                                         \
       SGP_XSTORE(XBUFS == 2 ? 1 - (BUF) : 0)                                                   \
       __syncthreads();                                                                         \
-    } else if (GLU) {                                                                          \
+    } else {                                                                                   \
       asm volatile("s_nop 9\n\ts_nop 9");                                                      \
     }
 
