@@ -130,7 +130,8 @@ class MLAttention(nn.Module):
         start_pos = int(positions.reshape(-1)[0])
       q_rot = _rope(q_rot, *_rope_rows(cos, sin, positions, B, S), cfg.rope_interleave)
       if not torch.is_grad_enabled():
-        # GPU prefill: query-chunked bf16 attention (the eager path below
+        # GPU prefill: the attn_prefill_mla kernel, or query-chunked bf16
+        # torch attention where it does not apply (the eager path below
         # materializes [B,H,S,T] fp32 scores — 67 GB transient per layer
         # at B=64, S=512)
         return self._prefill_absorbed(x, q_pass, q_rot, kv, start_pos, S)
@@ -167,13 +168,18 @@ class MLAttention(nn.Module):
 
 
   def _prefill_absorbed(self, x, q_pass, q_rot, kv, start_pos: int, S: int):
-    """GPU prefill: expand the latent cache through kv_b into per-head
-    K/V (qk dim 192 -> flash-eligible) and run sdpa causal; when the
-    query block is offset inside a longer cache (chunked serve prefill),
-    run query-chunked bf16 matmuls with an fp32 softmax so the O(S*T)
-    score tile never materializes in fp32 for the whole batch (measured
-    879->726 ms whole-batch TTFT at B=64 S=512 vs sdpa, whose flash
-    backend refuses head_dim 192 on ROCm and falls to math)."""
+    """GPU prefill, non-absorbed: expand the latent cache through kv_b
+    (a large-M library GEMM) into per-head k_nope | v, then causal
+    attention at qk 192 / v 128, whole prompts and offset chunks
+    (chunked serve prefill) alike. At nope 128 / rope 64 / v 128 in bf16
+    that is one attn_prefill_mla launch (hip_ops.hip), which reads the
+    GEMM output and the rope cache in place. Other dims, or
+    XOT_MLA_PREFILL=0, take the torch route below: cat the shared rope
+    key onto every head, then query-chunked bf16 matmuls with an fp32
+    softmax, so the O(S*T) score tile never materializes in fp32 for the
+    whole batch (sdpa's flash backend refuses head_dim 192 on ROCm and
+    its math backend measured slower: 879 vs 726 ms whole-batch TTFT at
+    B=64 S=512)."""
     cfg = self.cfg
     B, H = x.shape[0], cfg.n_heads
     nope, vd = cfg.qk_nope_head_dim, cfg.v_head_dim
@@ -181,6 +187,11 @@ class MLAttention(nn.Module):
     lat = kv.k[:, 0, :total]                                    # [B,T,512]
     rot = kv.v[:, 0, :total]                                    # [B,T,64]
     kvx = self.kv_b_proj(lat).view(B, total, H, nope + vd)
+    if (nope, cfg.qk_rope_head_dim, vd) == (128, 64, 128) and kvx.dtype == torch.bfloat16 \
+       and kv.v.dtype == torch.bfloat16 and ops.mla_prefill_enabled():
+      q = torch.cat([q_pass.to(x.dtype), q_rot.to(x.dtype)], dim=-1)  # [B,S,H,192], the one small cat
+      out = ops.attn_prefill_mla(q, kvx, kv.v, start_pos, self.scale)
+      return self.o_proj(out.view(B, S, H * vd))
     k = torch.cat([kvx[..., :nope],
                    rot[:, :, None, :].expand(B, total, H, -1)], dim=-1)
     k = k.permute(0, 2, 1, 3)                                   # [B,H,T,192]

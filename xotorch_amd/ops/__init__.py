@@ -256,6 +256,15 @@ mla_prep_append = _binding("mla_prep_append")
 # (q [B,S,H,qk], q_lat, cos, sin, int32 positions, nope, interleave, fp8) -> (q [B,H,576][, per-head scales when fp8])
 mla_q_prep = _binding("mla_q_prep")
 attn_decode_mla = _binding("attn_decode_mla")  # (q, kp, vp, seq_lens, scale, q_scale | None, k_scale | None) -> [B, H, lat]
+# causal flash prefill, nope 128 / rope 64 / v 128: (q [B,S,H,192], kvx [B,T,H,256] = the kv_b_proj output read in
+# place, rot [B,1,Tcap,64] = the plain rope-key cache, start_pos, scale) -> [B, S, H, 128], T = start_pos + S
+attn_prefill_mla = _binding("attn_prefill_mla")
+
+
+def mla_prefill_enabled() -> bool:
+  """XOT_MLA_PREFILL (default 1, read per call): MLA prefill attention on the
+  attn_prefill_mla kernel; 0 keeps the query-chunked torch matmuls."""
+  return os.getenv("XOT_MLA_PREFILL", "1") == "1"
 
 
 def _packed_epilogue(fn, x, wp, N, bias, epilogue):

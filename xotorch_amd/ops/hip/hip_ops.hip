@@ -1686,6 +1686,272 @@ __global__ __launch_bounds__(256) void attn_decode_mla_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// MLA flash-forward prefill (causal, non-absorbed): nope 128 | rope 64 keys,
+// 128-dim values — DeepSeek V2-Lite / V3 / R1.
+//
+// K and V live in no cache: they are the row-major kv_b_proj output
+// kvx [B, T, H, 256] = k_nope | v, read in place through its strides, and the
+// key's last 64 dims are the ONE roped vector per position of the plain rope
+// cache rot [B, 1, Tcap, 64], broadcast to the heads here instead of being
+// concatenated H times in memory. Grid: one 4-wave workgroup per (q block, b,
+// h) with the heads of a (q block, b) adjacent (the rot tile stays in L2) and
+// the late q blocks first (under the causal mask the last block walks S/QROWS
+// times the first one's tiles). A wave owns NT 16-row sub-tiles; the waves
+// share each 32-position K/V tile through LDS, double-buffered: the next
+// tile's global loads are issued before the MFMAs of this one and parked in
+// LDS after them, one barrier per tile.
+//   scores[16][32] = 2 x 6 v_mfma_f32_16x16x32_bf16 (4 chunks of kvx, 2 of rot)
+//   fp32 online softmax, masked before the maximum (a masked p is exactly 0)
+//   P -> bf16 through the 96 B-stride image, out[16][128] += 8 MFMAs
+// K operand: a lane wants 8 consecutive dims of one position, which row-major
+// rows give directly: 16 B loads, 16 B LDS stores, b128 reads.
+// V operand: the PV B fragment wants 8 consecutive POSITIONS of one dim, and V
+// arrives position-major. The tile is staged as it arrives and transposed by
+// the gfx950 transposing LDS read, ds_read_b64_tr_b16 (transposing on the
+// staging store instead measured 1% slower: docs/KERNELS.md).
+// ---------------------------------------------------------------------------
+
+constexpr int MLA_PF_NOPE = 128, MLA_PF_V = 128, MLA_PF_QK = MLA_PF_NOPE + MLA_ROPE;
+// K stage: 32 rows of 192 dims at a 200-element stride. A b128 read has its
+// 16 lanes of one k-offset on 16 consecutive rows; 400 B = 100 dwords moves a
+// row by 4 banks (mod 32) or 36 (mod 64), so any 8 (32 banks) or 16 (64 banks)
+// consecutive rows start on distinct 4-bank groups: conflict-free, and the
+// stride stays a multiple of 16 B for the b128 stores and reads.
+constexpr int MLA_PF_KROW = MLA_PF_QK + 8;
+// V stage, row-major for the transposing read: 32 position rows of 128 dims at
+// a 144-element stride. A 16-lane group reads 32 B (8 banks) from each of 4
+// consecutive rows; 288 B = 72 dwords = 8 mod 32 and mod 64 puts 4 (8) such
+// rows side by side on 32 (64) banks.
+constexpr int MLA_PF_VROW = MLA_PF_V + 16;
+typedef __attribute__((ext_vector_type(4))) short v4i16;
+typedef __attribute__((ext_vector_type(8))) short v8i16;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
+constexpr int MLA_PF_KSTAGE = 32 * MLA_PF_KROW;
+constexpr int MLA_PF_VSTAGE = 32 * MLA_PF_VROW;
+
+// 16-row sub-tiles per wave. Two (128-row q blocks) halve the K/V tile traffic
+// per query row and fit 2 waves/SIMD without scratch (resource table in
+// docs/KERNELS.md), the same occupancy the 55 KB of LDS allows.
+constexpr int MLA_PF_NT = 2;
+
+// Built without the packed fp32 VALU forms (v_pk_mul / add / fma_f32): the
+// accumulator rescale and the score scaling then run on plain v_mul_f32 (56
+// packed ops otherwise). This buys no speed and is not needed for occupancy:
+// with the packed forms the compiler reports 225 VGPRs instead of 220, scratch
+// 0 and 2 waves/SIMD either way. It is a choice for new code: this kernel's
+// results do not rest on the packed fp32 forms, whose operand-select variants
+// the older kernels have to be trusted on. A per-kernel attribute, so the
+// other kernels' opcode streams do not move (the host pass has no such feature).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MLA_PF_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define MLA_PF_NO_PK_F32
+#endif
+
+// Only force-inlined code joins a kernel whose target features differ, so the
+// kernel states its lane exchange, its barrier and its staging lambdas that way.
+DEVINL float mla_pf_lane_xor(float v, int lane, int mask) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ mask) << 2, __builtin_bit_cast(int, v)));
+}
+
+DEVINL void mla_pf_barrier() {  // __syncthreads
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <int NT>
+__global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_prefill_mla_kernel(
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ kvx,
+    const unsigned short* __restrict__ rot, unsigned short* __restrict__ out,
+    int B, int S, int H, int start_pos,
+    long long q_bstride, long long q_sstride, long long kv_bstride, long long kv_tstride,
+    long long rot_bstride, long long rot_tstride, float scale) {
+  static_assert(NT == 1 || NT == 2, "a wave owns one or two 16-row sub-tiles");
+  constexpr int NC = MLA_PF_QK / 32, NG = MLA_PF_V / 16;
+  constexpr int QROWS = 64 * NT;
+  constexpr int KROW = MLA_PF_KROW, VROW = MLA_PF_VROW;
+  // block -> (q block, b, h): heads fastest, late q blocks first
+  const int qblocks = (S + QROWS - 1) / QROWS;
+  const int h = blockIdx.x % H;
+  const int t1 = blockIdx.x / H;
+  const int b = t1 % B;
+  const int qb = qblocks - 1 - t1 / B;
+  const int tid = threadIdx.x;
+  const int wv = tid >> 6;
+  const int lane = tid & 63;
+  const int col = lane & 15, quad = lane >> 4;
+  const int T = start_pos + S;
+
+  __shared__ __attribute__((aligned(16))) unsigned short kv_lds[2][MLA_PF_KSTAGE + MLA_PF_VSTAGE];
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][16 * 48 * NT];
+
+  // this wave's 16 * NT q rows [r0, r0 + 16 * NT); rows clamped to S - 1
+  // (their stores are predicated, the extra rows only waste compute)
+  const int r0 = qb * QROWS + wv * (16 * NT);
+  bf16x8 qf[NT][NC];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int row = min(r0 + t * 16 + col, S - 1);
+    const unsigned short* qrow = q + (size_t)b * q_bstride + (size_t)row * q_sstride + (size_t)h * MLA_PF_QK;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) qf[t][c] = frag_load<false>(qrow + c * 32 + quad * 8);
+  }
+
+  float m[NT][4], lsum[NT][4];
+  floatx4 acco[NT][NG];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[t][r] = -INFINITY; lsum[t][r] = 0.f; }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int g = 0; g < NG; ++g) acco[t][g] = (floatx4)(0.f);
+
+  // causal end of the BLOCK (its last real row): positions [0, kv_end), kv_end <= T
+  const int kv_end = start_pos + min(qb * QROWS + QROWS, S);
+  const int ntiles = (kv_end + 31) >> 5;
+
+  // A tile's 1280 16-byte pieces, 5 per thread, every position clamped to
+  // T - 1, the last row of kvx and the last written row of rot (clamped
+  // positions are >= kv_end and masked below):
+  //   k_nope, v 512 each: piece e = tid + 256 i -> position e >> 4, dims (e & 15) * 8
+  //   rope      256:      position tid >> 3, dims (tid & 7) * 8
+  const unsigned short* kvb = kvx + (size_t)b * kv_bstride + (size_t)h * (MLA_PF_NOPE + MLA_PF_V);
+  const unsigned short* rotb = rot + (size_t)b * rot_bstride;
+  ushort8 sk[2], sr, sv[2];
+  auto stage_load = [&](int tp) __attribute__((always_inline)) {
+    const int p0 = tp * 32;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int e = tid + i * 256;
+      const size_t prow = (size_t)min(p0 + (e >> 4), T - 1) * kv_tstride;
+      sk[i] = *(const ushort8*)(kvb + prow + (e & 15) * 8);
+      sv[i] = *(const ushort8*)(kvb + prow + MLA_PF_NOPE + (e & 15) * 8);
+    }
+    sr = *(const ushort8*)(rotb + (size_t)min(p0 + (tid >> 3), T - 1) * rot_tstride + (tid & 7) * 8);
+  };
+  auto stage_store = [&](int buf) __attribute__((always_inline)) {
+    unsigned short* dk = kv_lds[buf];
+    unsigned short* dv = kv_lds[buf] + MLA_PF_KSTAGE;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int e = tid + i * 256;
+      *(ushort8*)(dk + (e >> 4) * KROW + (e & 15) * 8) = sk[i];
+      *(ushort8*)(dv + (e >> 4) * VROW + (e & 15) * 8) = sv[i];
+    }
+    *(ushort8*)(dk + (tid >> 3) * KROW + MLA_PF_NOPE + (tid & 7) * 8) = sr;
+  };
+
+  stage_load(0);
+  stage_store(0);
+  mla_pf_barrier();
+
+  unsigned short* plds = plds_all[wv];
+  for (int tp = 0; tp < ntiles; ++tp) {
+    const int buf = tp & 1;
+    const bool more = tp + 1 < ntiles;
+    if (more) stage_load(tp + 1);  // in flight under this tile's MFMAs
+    const unsigned short* dk = kv_lds[buf];
+    const unsigned short* dv = kv_lds[buf] + MLA_PF_KSTAGE;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      // wave-uniform: a tile wholly above the sub-tile's last row is all masked
+      // (p = 0, alpha = 1). Tile 0 is never skipped, so m is finite afterwards
+      // and no row meets an all-masked tile with m = -inf.
+      if (tp * 32 > start_pos + r0 + t * 16 + 15) continue;
+      floatx4 sc[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        sc[hh] = (floatx4)(0.f);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const bf16x8 kb = *reinterpret_cast<const bf16x8*>(dk + (hh * 16 + col) * KROW + c * 32 + quad * 8);
+          sc[hh] = Frag<false>::mfma(qf[t][c], kb, sc[hh]);
+        }
+      }
+      // causal mask: position <= start_pos + row (which also keeps it < T)
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int pos = tp * 32 + hh * 16 + col;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = r0 + t * 16 + quad * 4 + r;
+          sc[hh][r] = (pos <= start_pos + row) ? sc[hh][r] * scale : -INFINITY;
+        }
+      }
+      float rmax[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(sc[0][r], sc[1][r]);
+#pragma unroll
+      for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(rmax[r], mla_pf_lane_xor(rmax[r], lane, mm));
+      float alpha[4], rsum[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float mn = fmaxf(m[t][r], rmax[r]);
+        alpha[r] = (lsum[t][r] > 0.f) ? __expf(m[t][r] - mn) : 0.f;
+        m[t][r] = mn;
+        const float p0 = __expf(sc[0][r] - mn);
+        const float p1 = __expf(sc[1][r] - mn);
+        sc[0][r] = p0;
+        sc[1][r] = p1;
+        rsum[r] = p0 + p1;
+      }
+#pragma unroll
+      for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rsum[r] += mla_pf_lane_xor(rsum[r], lane, mm);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) lsum[t][r] = lsum[t][r] * alpha[r] + rsum[r];
+      attn_rescale(acco[t], alpha, 1.f);
+      unsigned short* pl = plds + t * 16 * 48;  // one P image per sub-tile
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          pl[(quad * 4 + r) * 48 + hh * 16 + col] = f2b(sc[hh][r]);
+      // ds_read_b64_tr_b16: in a 16-lane group, lane L points at 4 dims of
+      // position row L >> 2 (dims 4 (L & 3) ..) and lane i receives dim i of
+      // those 4 rows. Quad qd takes rows 4 qd .. and 16 + 4 qd .., so the 32
+      // lanes of a half-wave read 8 consecutive rows; the contraction index
+      // only has to agree with P's, which is read from its image in that order.
+      const bf16x4 plo = *reinterpret_cast<const bf16x4*>(pl + col * 48 + quad * 4);
+      const bf16x4 phi = *reinterpret_cast<const bf16x4*>(pl + col * 48 + 16 + quad * 4);
+      const bf16x8 pf = __builtin_shufflevector(plo, phi, 0, 1, 2, 3, 4, 5, 6, 7);
+      const unsigned short* vrow = dv + (quad * 4 + (col >> 2)) * VROW + (col & 3) * 4;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const v4i16 vlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(vrow + g * 16));
+        const v4i16 vhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(vrow + 16 * VROW + g * 16));
+        const v8i16 vb = __builtin_shufflevector(vlo, vhi, 0, 1, 2, 3, 4, 5, 6, 7);
+        acco[t][g] = Frag<false>::mfma(pf, __builtin_bit_cast(bf16x8, vb), acco[t][g]);
+      }
+    }
+    if (more) stage_store(buf ^ 1);  // last read before the previous barrier
+    mla_pf_barrier();
+  }
+
+  // epilogue: out[b, row, h, g * 16 + col] = acc / lsum, rows past S dropped
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = r0 + t * 16 + quad * 4 + r;
+      if (row < S) {
+        const float inv = 1.f / lsum[t][r];
+        unsigned short* orow = out + (((size_t)b * S + row) * H + h) * MLA_PF_V;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) orow[g * 16 + col] = f2b(acco[t][g][r] * inv);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // SwiGLU: silu(gate) * up, elementwise, vectorized
 // ---------------------------------------------------------------------------
 
@@ -3101,6 +3367,42 @@ torch::Tensor attn_decode_mla(torch::Tensor q, torch::Tensor kp, torch::Tensor v
   return kv.merge(stream);
 }
 
+// q: [B, S, H, 192] bf16 (q_pass | roped q_rot; strided over b/s OK, head rows
+// contiguous); kvx: [B, T, H, 256] bf16, the kv_b_proj output (k_nope | v),
+// T = start_pos + S, strided over b/t OK; rot: [B, 1, Tcap, 64] bf16, the plain
+// rope-key cache, holding positions [0, T). Returns out [B, S, H, 128] bf16.
+torch::Tensor attn_prefill_mla(torch::Tensor q, torch::Tensor kvx, torch::Tensor rot,
+                               int64_t start_pos, double scale) {
+  CHK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.dim() == 4);
+  CHK(kvx.is_cuda() && kvx.dtype() == torch::kBFloat16 && kvx.dim() == 4);
+  CHK(rot.is_cuda() && rot.dtype() == torch::kBFloat16 && rot.dim() == 4);
+  const int B = q.size(0), S = q.size(1), H = q.size(2);
+  const int64_t T = start_pos + S;
+  TORCH_CHECK(q.size(3) == MLA_PF_QK && kvx.size(3) == MLA_PF_NOPE + MLA_PF_V && rot.size(3) == MLA_ROPE,
+              "attn_prefill_mla: nope 128 / rope 64 / v 128 only, got q ", q.size(3), ", kvx ", kvx.size(3),
+              ", rot ", rot.size(3));
+  CHK(B > 0 && S > 0 && H > 0 && start_pos >= 0 && scale > 0.0);
+  CHK(kvx.size(0) == B && kvx.size(1) == T && kvx.size(2) == H);
+  CHK(rot.size(0) == B && rot.size(1) == 1);
+  TORCH_CHECK(T <= rot.size(2), "attn_prefill_mla: T = ", T, " exceeds the rope cache's capacity ", rot.size(2));
+  CHK(q.stride(3) == 1 && q.stride(2) == MLA_PF_QK);
+  CHK(kvx.stride(3) == 1 && kvx.stride(2) == MLA_PF_NOPE + MLA_PF_V && rot.stride(3) == 1);
+  // 16-byte loads: aligned bases, row strides in whole 8-element pieces
+  for (const torch::Tensor* t : {&q, &kvx, &rot}) CHK((uintptr_t)t->data_ptr() % 16 == 0);
+  for (int64_t s : {q.stride(0), q.stride(1), kvx.stride(0), kvx.stride(1), rot.stride(0), rot.stride(2)})
+    CHK(s % 8 == 0);
+  auto out = torch::empty({B, S, H, MLA_PF_V}, q.options());
+  constexpr int QROWS = 64 * MLA_PF_NT;
+  const int64_t blocks = (int64_t)B * ((S + QROWS - 1) / QROWS) * H;
+  CHK(blocks <= INT_MAX);
+  hipLaunchKernelGGL((attn_prefill_mla_kernel<MLA_PF_NT>), dim3((unsigned)blocks), dim3(256), 0, cur_stream(),
+                     (const unsigned short*)q.data_ptr(), (const unsigned short*)kvx.data_ptr(),
+                     (const unsigned short*)rot.data_ptr(), (unsigned short*)out.data_ptr(), B, S, H,
+                     (int)start_pos, q.stride(0), q.stride(1), kvx.stride(0), kvx.stride(1), rot.stride(0),
+                     rot.stride(2), (float)scale);
+  return out;
+}
+
 torch::Tensor mfma16_probe(torch::Tensor a, torch::Tensor b) {
   CHK(a.is_cuda() && a.dtype() == torch::kBFloat16 && a.is_contiguous() && a.numel() == 16 * 32);
   CHK(b.is_cuda() && b.dtype() == torch::kBFloat16 && b.is_contiguous() && b.numel() == 32 * 16);
@@ -3687,6 +3989,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MLA decode attention (absorbed latent MQA) on matrix cores; fp8 cache mode",
         py::arg("q"), py::arg("kp"), py::arg("vp"), py::arg("seq_lens"),
         py::arg("scale") = 0.0, py::arg("q_scale") = py::none(), py::arg("k_scale") = py::none());
+  m.def("attn_prefill_mla", &attn_prefill_mla,
+        "MLA causal flash prefill (qk 192 = nope 128 | shared rope 64, v 128) on matrix cores, "
+        "K/V read in place from the kv_b_proj output and the plain rope cache",
+        py::arg("q"), py::arg("kvx"), py::arg("rot"), py::arg("start_pos"), py::arg("scale"));
   m.def("mfma16_probe", &mfma16_probe, "v_mfma_f32_16x16x32_bf16 layout probe (tests)");
   m.def("swiglu", &swiglu, "SwiGLU activation");
 }
