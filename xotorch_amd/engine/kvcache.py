@@ -48,9 +48,12 @@ class ShardKVCache:
     roped key — see ModelConfig.kv_cache_dims()).
     plain=False: a packed-only cache, LayerKV.k / .v are None. For callers
     whose append and attention read only (kp, vp): the llama decoder with MFMA
-    attention. Honoured only where the bf16 GQA packed copies are allocated
-    and XOT_FP8_KV is off (fp8-KV prefill reads the plain cache); anywhere
-    else the argument is ignored and the plain tensors are allocated."""
+    attention. Honoured only where the GQA packed copies are allocated: the
+    bf16 ones, or under XOT_FP8_KV=1 the e4m3 ones when XOT_FP8_KV_PREFILL=1
+    sends prefill to the kernel that reads them (k / v None, kp / vp uint8,
+    scales present: 1 byte per element plus the scales; without that knob
+    fp8-KV prefill reads the plain cache). Anywhere else the argument is
+    ignored and the plain tensors are allocated."""
     self.capacity = capacity
     self.batch = batch
     self.caches: List[LayerKV] = []
@@ -77,10 +80,11 @@ class ShardKVCache:
       kp_shape = vp_shape = None
       scale_shapes = []
     # fp8-KV: e4m3 packed copies (half the decode stream) + per-row scales;
-    # the plain cache stays in `dtype` for prefill
+    # the plain cache stays in `dtype` for prefill unless XOT_FP8_KV_PREFILL=1
     fp8_kv = kp_shape is not None and os.getenv("XOT_FP8_KV", "0") == "1"
     gqa_packed = kp_shape is not None and len(kp_shape) == 6
-    self.plain = plain or not (gqa_packed and dtype == torch.bfloat16 and not fp8_kv)
+    self.plain = plain or not (gqa_packed and dtype == torch.bfloat16
+                               and (not fp8_kv or ops.fp8_kv_prefill_enabled()))
     for _ in range(n_layers):
       layer = [None, None]
       if self.plain:
@@ -121,5 +125,5 @@ class ShardKVCache:
   def nbytes(self) -> int:
     total = 0
     for c in self.caches:
-      total += sum(t.numel() * t.element_size() for t in (c.k, c.v, c.kp, c.vp) if t is not None)
+      total += sum(t.numel() * t.element_size() for t in c if t is not None)
     return total

@@ -87,7 +87,8 @@ class Gemma2Attention(nn.Module):
                               k_scale=kv.ksc, v_scale=kv.vsc)
       else:
         out = ops.attn_prefill(q, k_cache, v_cache, start_pos, S, kv.kp, kv.vp,
-                               scale=self.scale, softcap=cap, window=self.window)
+                               scale=self.scale, softcap=cap, window=self.window,
+                               k_scale=kv.ksc, v_scale=kv.vsc)
       return self.o_proj(out.reshape(B, S, H * hd))
     # eager oracle path (CPU / hd outside ops.PACKED_HEAD_DIMS): split the fused projection
     if start_pos < 0:  # ring/serve decode contract: derive from positions

@@ -99,7 +99,7 @@ class Attention(nn.Module):
       sl = seq_lens if seq_lens is not None else start_pos + 1
       out = ops.attn_decode(q, kv.k, kv.v, sl, kv.kp, kv.vp, k_scale=kv.ksc, v_scale=kv.vsc)
     else:
-      out = ops.attn_prefill(q, kv.k, kv.v, start_pos, S, kv.kp, kv.vp)
+      out = ops.attn_prefill(q, kv.k, kv.v, start_pos, S, kv.kp, kv.vp, k_scale=kv.ksc, v_scale=kv.vsc)
     return self.o_proj(out.reshape(B, S, H * hd))
 
 

@@ -145,17 +145,32 @@ def rope_qkv_append(qkv, cos, sin, positions, k_cache, v_cache, n_heads: int, n_
                             head_dim, q_norm, k_norm, norm_eps)
 
 
+def fp8_kv_prefill_enabled() -> bool:
+  """XOT_FP8_KV_PREFILL (default 0, read per call): under XOT_FP8_KV=1, prefill
+  attention streams the e4m3 packed cache (attn_prefill_mfma's fp8-KV kernel)
+  instead of the plain bf16 cache, and ShardKVCache(plain=False) drops the
+  plain tensors. (XOT_FP8_PREFILL is the scaled-mm prefill GEMMs.)"""
+  return os.getenv("XOT_FP8_KV_PREFILL", "0") == "1"
+
+
 def attn_prefill(q, k_cache, v_cache, start_pos: int, s_len: int, kp=None, vp=None,
-                 scale=None, softcap: float = 0.0, window: int = 0):
+                 scale=None, softcap: float = 0.0, window: int = 0, k_scale=None, v_scale=None):
+  """k_scale / v_scale: the fp8-KV cache's per-position scales [B, KVH, T32]."""
   if q.is_cuda and q.dtype == torch.bfloat16 and kp is not None and q.shape[3] in PACKED_HEAD_DIMS \
-     and kp.dtype == torch.bfloat16 and mfma_attn_enabled() and _use_hip(q):
+     and mfma_attn_enabled():
     # causal flash-forward on matrix cores, streaming the MFMA-packed cache;
-    # softcap/window run gemma2 semantics inside the same kernel (fp8-KV
-    # mode keeps prefill on the plain bf16 cache via the sdpa path below)
-    return _hip.attn_prefill_mfma(q, kp, vp, start_pos, scale or 0.0, softcap, window)
+    # softcap/window run gemma2 semantics inside the same kernel
+    if kp.dtype == torch.bfloat16 and _use_hip(q):
+      return _hip.attn_prefill_mfma(q, kp, vp, start_pos, scale or 0.0, softcap, window)
+    # fp8-KV: the e4m3 copies and their scales, dequantised as they are staged.
+    # Taken by a packed-only cache and, beside plain tensors, on XOT_FP8_KV_PREFILL=1;
+    # otherwise fp8-KV prefill stays on the plain bf16 cache below.
+    if kp.dtype == torch.uint8 and k_scale is not None and v_scale is not None \
+       and (k_cache is None or fp8_kv_prefill_enabled()) and _use_hip(q):
+      return _hip.attn_prefill_mfma(q, kp, vp, start_pos, scale or 0.0, softcap, window, k_scale, v_scale)
   _need_plain_cache("attn_prefill", k_cache,
-                    "only the MFMA prefill kernel (XOT_MFMA_ATTN=1, bf16 packed copies, head_dim 128 or 256) "
-                    "reads the packed copies")
+                    "only the MFMA prefill kernels (XOT_MFMA_ATTN=1, head_dim 128 or 256; bf16 packed copies, "
+                    "or e4m3 copies passed with k_scale and v_scale) read the packed copies")
   if q.is_cuda and not softcap and not window:
     # fallback: sdpa (rocm flash/mem-efficient backends) in model dtype with
     # native GQA — hd outside PACKED_HEAD_DIMS or unpacked-cache path

@@ -122,6 +122,21 @@ DEVINL long to_e4m3x8(bf16x8 v, float inv) {
   return *reinterpret_cast<const long*>(o);
 }
 
+// 8 e4m3 bytes (two dwords) -> 8 bf16, exact: e4m3 has 3 mantissa bits and bf16
+// the range, subnormals included. gfx950's packed convert at scale 1.0, the
+// sibling of w4_frag's v_cvt_scalef32_pk_bf16_fp4. (Not cvt_pk_f32_fp8 and the
+// two high halves joined by shift / and / or: this compiler folds that
+// expression to element 0 in both halves; a v_perm_b32 join is compiled right.)
+DEVINL uintx4 e4m3x8_to_bf16x8(unsigned int lo, unsigned int hi) {
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+  uintx4 o;
+  o[0] = __builtin_bit_cast(unsigned int, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false));
+  o[1] = __builtin_bit_cast(unsigned int, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true));
+  o[2] = __builtin_bit_cast(unsigned int, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false));
+  o[3] = __builtin_bit_cast(unsigned int, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true));
+  return o;
+}
+
 // positions: [S] (shared across batch) or [B*S] (per-row — continuous
 // batching where every slot decodes at its own position); bs = b * S + s
 DEVINL int row_position(const int* __restrict__ positions, int npos, int B, int S, int bs) {
@@ -218,7 +233,9 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(
 // scales while rotating.
 // fp8 packed mode (kp8 non-null): the packed copies are OCP e4m3 bytes with
 // per-row scales sk/sv [B*KVH*T32] — half the decode stream and ~60% of the
-// dual-cache residency (plain cache stays bf16 for prefill). XOT_FP8_KV=1.
+// dual-cache residency (the plain cache, where there is one, stays bf16; a
+// packed-only fp8 cache has kc / vc null and takes only these stores).
+// XOT_FP8_KV=1.
 
 // this lane's rotated pairs (pair e: dims p, p + hd/2, p = lane + 64 e) of one
 // q or k head row, after the optional per-head RMSNorm (w non-null) over the
@@ -1952,6 +1969,241 @@ __global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_prefill_mla_kern
 }
 
 // ---------------------------------------------------------------------------
+// fp8-KV flash prefill (HD = 128 or 256, causal, GQA): attn_prefill_mfma_kernel
+// over the e4m3 packed cache and its per-position scales sk / sv [B, KVH, T32].
+//
+// Same split as the bf16 kernel: one 4-wave workgroup per (q block, b, h),
+// ATTN_PREFILL_NT sub-tiles per wave, 32-position K/V tiles double-buffered in
+// LDS, causal / window tile skipping, final bf16 rows. The codes are
+// dequantised while they are staged: LDS holds the bf16 fragment image the
+// bf16 kernel holds (the conversion is exact), so the score and PV loops run
+// v_mfma_f32_16x16x32_bf16 on conflict-free b128 reads, and q keeps its bf16
+// bits (decode quantises q because it is stream-bound; prefill is not).
+//   staging  a tile is 2 * KTILE bytes of K and NG * FRAG bytes of V: one 16 B
+//            global load each per thread at HD 128, two at 256. A load holds
+//            two lanes' 8 B fragments and becomes 32 B of the bf16 image at the
+//            same element offset (two b128 stores). The next tile's loads are
+//            issued before this tile's MFMAs and converted and stored after
+//            them, as in attn_prefill_mla_kernel.
+//   scales   threads 0..63 carry the tile's 32 K and 32 V scales with the same
+//            load / store pair into a 256 B LDS row per buffer; a lane reads
+//            its two columns' scales from there (4 ds_read_b32 per tile, no
+//            global latency inside the loop).
+//   K scale  s = acc * scale * sk[pos] in fp32, before softcap and the mask.
+//   V scale  folded into P before its one rounding: the image holds
+//            bf16(p * sv[pos]). bf16 has the range, so acco stays in true
+//            units: no running PV scale as the e4m3-P decode kernels need.
+// A masked position contributes exact 0 whatever codes and scales lie there:
+// its score is -inf before the maximum, and p = 0 times a finite scale is 0.
+// Every global read stays inside [0, T32) of its own (b, kv-head): tiles end
+// at ceil(kv_end / 32) <= T32 / 32.
+// Built without the packed fp32 VALU forms, like attn_prefill_mla_kernel, and
+// therefore on force-inlined helpers only (tanh included).
+// ---------------------------------------------------------------------------
+
+// tanh for the softcap: 1 - 2 / (1 + e^2x), saturating to +-1 as e^2x -> inf, 0
+DEVINL float kv8_tanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
+
+template <int HD, int NT>
+__global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_prefill_mfma_kv8_kernel(
+    const unsigned short* __restrict__ q, const unsigned char* __restrict__ kp,
+    const unsigned char* __restrict__ vp, const float* __restrict__ sk, const float* __restrict__ sv,
+    unsigned short* __restrict__ out, int B, int S, int H, int KVH, int T32, int start_pos,
+    long long q_bstride, long long q_sstride, float scale, float softcap, int window) {
+  static_assert(GQA_PACKED_HD(HD), "packed GQA cache: head_dim 128 or 256");
+  constexpr int NC = HD / 32, NG = GQA_VGROUPS(HD), KTILE = GQA_KTILE(HD);  // qk chunks, pv groups
+  static_assert(NT == 1 || NT == 2, "a wave owns one or two 16-row sub-tiles");
+  constexpr int QSHIFT = NT == 2 ? 7 : 6, QROWS = 1 << QSHIFT;  // q rows per block: 4 waves x NT x 16
+  constexpr int KV_K = 2 * KTILE, KV_V = NG * FRAG;             // elements = code bytes of a tile
+  constexpr int KLOADS = KV_K / 4096, VLOADS = KV_V / 4096;     // 16 B loads per thread
+  // block -> (b, h, q-block)
+  const int qblocks = (S + QROWS - 1) >> QSHIFT;
+  const int h = blockIdx.x % H;
+  const int t1 = blockIdx.x / H;
+  const int qb = t1 % qblocks;
+  const int b = t1 / qblocks;
+  const int tid = threadIdx.x;
+  const int wv = tid >> 6;
+  const int lane = tid & 63;
+  const int col = lane & 15, quad = lane >> 4;
+  const int kvh = h / (H / KVH);
+
+  __shared__ __attribute__((aligned(16))) unsigned short kv_lds[2][KV_K + KV_V];  // dbuf, bf16 fragments
+  __shared__ float sc_lds[2][64];                                                  // [buf][K scales 32 | V scales 32]
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][16 * 48 * NT];
+
+  // this wave's 16 * NT q rows [r0, r0 + 16 * NT); rows clamped to S - 1
+  // (their stores are predicated, the extra rows only waste compute)
+  const int r0 = qb * QROWS + wv * (16 * NT);
+  bf16x8 qf[NT][NC];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int row = min(r0 + t * 16 + col, S - 1);
+    const unsigned short* qrow = q + (size_t)b * q_bstride + (size_t)row * q_sstride + (size_t)h * HD;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) qf[t][c] = frag_load<false>(qrow + c * 32 + quad * 8);
+  }
+
+  float m[NT][4], lsum[NT][4];
+  floatx4 acco[NT][NG];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[t][r] = -INFINITY; lsum[t][r] = 0.f; }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int g = 0; g < NG; ++g) acco[t][g] = (floatx4)(0.f);
+
+  const size_t head = (size_t)(b * KVH + kvh);
+  const unsigned char* khead = kp + head * (T32 >> 4) * KTILE;
+  const unsigned char* vhead = vp + head * NG * (T32 >> 5) * FRAG;
+  // threads 0..31 carry the tile's K scales, 32..63 its V scales
+  const float* srow = (tid < 32 ? sk : sv) + head * T32 + (tid & 31);
+  // causal end for the BLOCK (max row): positions [0, start_pos + block_hi]
+  const int block_hi = min(qb * QROWS + QROWS - 1, S - 1);
+  const int kv_end = start_pos + block_hi + 1;  // exclusive, <= T32
+  const int ntiles = (kv_end + 31) >> 5;
+  // sliding window: the block's lowest q row sees nothing before
+  // start_pos + qb*QROWS - window + 1 — skip whole kv tiles below it
+  const int tp0 = (window > 0) ? max(0, (start_pos + qb * QROWS - window + 1) >> 5) : 0;
+
+  uintx4 kreg[KLOADS], vreg[VLOADS];
+  float sreg = 0.f;
+  auto stage_load = [&](int tp) __attribute__((always_inline)) {
+    const unsigned char* ksrc = khead + (size_t)(tp * 2) * KTILE;
+    const unsigned char* vsrc = vhead + (size_t)tp * FRAG;
+#pragma unroll
+    for (int i = 0; i < KLOADS; ++i) kreg[i] = *(const uintx4*)(ksrc + (tid + i * 256) * 16);
+#pragma unroll
+    for (int i = 0; i < VLOADS; ++i) {
+      const int e = tid + i * 256;  // (group, 16 B piece): 32 pieces per group
+      vreg[i] = *(const uintx4*)(vsrc + (size_t)(e >> 5) * (T32 >> 5) * FRAG + (e & 31) * 16);
+    }
+    if (tid < 64) sreg = srow[tp * 32];
+  };
+  // 16 codes -> the 16 bf16 at the same element offset of the fragment image
+  auto stage_store = [&](int buf) __attribute__((always_inline)) {
+    unsigned short* dk = kv_lds[buf];
+    unsigned short* dv = kv_lds[buf] + KV_K;
+#pragma unroll
+    for (int i = 0; i < KLOADS; ++i) {
+      unsigned short* d = dk + (tid + i * 256) * 16;
+      *(uintx4*)d = e4m3x8_to_bf16x8(kreg[i][0], kreg[i][1]);
+      *(uintx4*)(d + 8) = e4m3x8_to_bf16x8(kreg[i][2], kreg[i][3]);
+    }
+#pragma unroll
+    for (int i = 0; i < VLOADS; ++i) {
+      const int e = tid + i * 256;
+      unsigned short* d = dv + (e >> 5) * FRAG + (e & 31) * 16;
+      *(uintx4*)d = e4m3x8_to_bf16x8(vreg[i][0], vreg[i][1]);
+      *(uintx4*)(d + 8) = e4m3x8_to_bf16x8(vreg[i][2], vreg[i][3]);
+    }
+    if (tid < 64) sc_lds[buf][tid] = sreg;
+  };
+
+  stage_load(tp0);
+  stage_store(tp0 & 1);
+  mla_pf_barrier();
+
+  unsigned short* plds = plds_all[wv];
+  for (int tp = tp0; tp < ntiles; ++tp) {
+    const int buf = tp & 1;
+    const bool more = tp + 1 < ntiles;
+    if (more) stage_load(tp + 1);  // in flight under this tile's MFMAs
+    const unsigned short* dk = kv_lds[buf];
+    const unsigned short* dv = kv_lds[buf] + KV_K;
+    // this lane's two score columns: positions tp * 32 + hh * 16 + col
+    const float ksc[2] = {sc_lds[buf][col], sc_lds[buf][16 + col]};
+    const float vsc[2] = {sc_lds[buf][32 + col], sc_lds[buf][48 + col]};
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      floatx4 sc[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        sc[hh] = (floatx4)(0.f);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const bf16x8 kb = *reinterpret_cast<const bf16x8*>(dk + (hh * NC + c) * FRAG + lane * 8);
+          sc[hh] = Frag<false>::mfma(qf[t][c], kb, sc[hh]);
+        }
+      }
+      // K scale, softcap, then the causal / window mask: kv pos <= start_pos + row
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int pos = tp * 32 + hh * 16 + col;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = r0 + t * 16 + quad * 4 + r;
+          bool ok = (pos <= start_pos + row) && (pos < kv_end);
+          if (window > 0) ok = ok && (pos > start_pos + row - window);
+          float s = sc[hh][r] * scale * ksc[hh];
+          if (softcap > 0.f) s = softcap * kv8_tanh(s * (1.f / softcap));
+          sc[hh][r] = ok ? s : -INFINITY;
+        }
+      }
+      float rmax[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(sc[0][r], sc[1][r]);
+#pragma unroll
+      for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(rmax[r], mla_pf_lane_xor(rmax[r], lane, mm));
+      float alpha[4], rsum[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float mn = fmaxf(m[t][r], rmax[r]);
+        // nothing visible yet (a window block's first tiles): p = 0, state kept
+        if (mn == -INFINITY) { alpha[r] = 1.f; rsum[r] = 0.f; sc[0][r] = 0.f; sc[1][r] = 0.f; continue; }
+        alpha[r] = (lsum[t][r] > 0.f) ? __expf(m[t][r] - mn) : 0.f;
+        m[t][r] = mn;
+        const float p0 = __expf(sc[0][r] - mn);
+        const float p1 = __expf(sc[1][r] - mn);
+        sc[0][r] = p0;
+        sc[1][r] = p1;
+        rsum[r] = p0 + p1;
+      }
+#pragma unroll
+      for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rsum[r] += mla_pf_lane_xor(rsum[r], lane, mm);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) lsum[t][r] = lsum[t][r] * alpha[r] + rsum[r];
+      attn_rescale(acco[t], alpha, 1.f);
+      unsigned short* pl = plds + t * 16 * 48;  // one P image per sub-tile
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          pl[(quad * 4 + r) * 48 + hh * 16 + col] = f2b(sc[hh][r] * vsc[hh]);
+      const bf16x8 pf = *reinterpret_cast<const bf16x8*>(pl + col * 48 + quad * 8);
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const bf16x8 vb = *reinterpret_cast<const bf16x8*>(dv + g * FRAG + lane * 8);
+        acco[t][g] = Frag<false>::mfma(pf, vb, acco[t][g]);
+      }
+    }
+    if (more) stage_store(buf ^ 1);  // last read before the previous barrier
+    mla_pf_barrier();
+  }
+
+  // epilogue: out[b, row, h, g*16 + col] = acc / lsum
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = r0 + t * 16 + quad * 4 + r;
+      if (row < S) {
+        const float inv = (lsum[t][r] > 0.f) ? 1.f / lsum[t][r] : 0.f;
+        unsigned short* orow = out + (((size_t)b * S + row) * H + h) * HD;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) orow[g * 16 + col] = f2b(acco[t][g][r] * inv);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // SwiGLU: silu(gate) * up, elementwise, vectorized
 // ---------------------------------------------------------------------------
 
@@ -3161,31 +3413,58 @@ torch::Tensor attn_decode_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor 
 }
 
 // q: [B, S, H, hd], hd 128 or 256 (strided over b/s OK, head rows contiguous); kp/vp: the
-// packed cache copies already holding positions [0, start_pos + S).
+// packed cache copies already holding positions [0, start_pos + S): bf16, or e4m3 bytes
+// (uint8) with their per-position scales k_scale / v_scale [B, KVH, T32].
 torch::Tensor attn_prefill_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor vp,
                                 int64_t start_pos, double scale_in, double softcap,
-                                int64_t window) {
+                                int64_t window,
+                                c10::optional<torch::Tensor> k_scale,
+                                c10::optional<torch::Tensor> v_scale) {
   CHK(q.is_cuda() && q.dtype() == torch::kBFloat16);
   CHK(q.stride(3) == 1 && q.stride(2) == q.size(3));
-  CHK(kp.is_contiguous() && vp.is_contiguous());
   const int B = q.size(0), S = q.size(1), H = q.size(2), hd = q.size(3);
   TORCH_CHECK(GQA_PACKED_HD(hd), "attn_prefill_mfma: head_dim must be 128 or 256, got ", hd);
-  TORCH_CHECK(kp.dtype() == torch::kBFloat16, "attn_prefill_mfma: bf16 packed cache copies only");
+  const bool fp8 = kp.dtype() == torch::kUInt8;
+  TORCH_CHECK((fp8 || kp.dtype() == torch::kBFloat16) && vp.dtype() == kp.dtype(),
+              "attn_prefill_mfma: packed cache copies are bf16, or e4m3 bytes in uint8 tensors");
+  TORCH_CHECK(fp8 == k_scale.has_value() && fp8 == v_scale.has_value(),
+              "attn_prefill_mfma: e4m3 (uint8) packed copies come with k_scale and v_scale, bf16 copies without");
   check_packed_gqa_shapes("attn_prefill_mfma", kp, vp, hd);
+  const PackedCachePtrs pc = packed_cache_ptrs(kp, vp);
   const int KVH = kp.size(1);
   const int T32 = kp.size(2) * 16;
-  CHK(start_pos + S <= T32);
+  TORCH_CHECK(kp.size(0) >= B && vp.size(0) == kp.size(0) && vp.size(1) == KVH && H % KVH == 0,
+              "attn_prefill_mfma: q [", B, ", ", S, ", ", H, ", ", hd, "] does not match the cache's batch ",
+              kp.size(0), " and kv heads ", KVH);
+  CHK(start_pos >= 0 && S >= 1 && start_pos + S <= T32);
   auto out = torch::empty({B, S, H, hd},
                           torch::TensorOptions().dtype(torch::kBFloat16).device(q.device()));
   const float scale = (scale_in > 0.0) ? (float)scale_in : 1.0f / sqrtf((float)hd);
+  const float* skp = nullptr;
+  const float* svp = nullptr;
+  if (fp8) {
+    skp = fp8_scale_ptr(k_scale);
+    svp = fp8_scale_ptr(v_scale);
+    for (const auto* s : {&*k_scale, &*v_scale})
+      TORCH_CHECK(s->is_cuda() && s->dim() == 3 && s->size(0) == kp.size(0) && s->size(1) == KVH && s->size(2) == T32,
+                  "attn_prefill_mfma: k_scale / v_scale must be [B, KVH, T32] = [", kp.size(0), ", ", KVH, ", ", T32, "]");
+  }
   dispatch_packed_hd(hd, "attn_prefill_mfma", [&](auto hdc) {
     constexpr int HD = decltype(hdc)::value, NT = ATTN_PREFILL_NT(HD);
     const int qblocks = (S + 64 * NT - 1) / (64 * NT);
-    hipLaunchKernelGGL((attn_prefill_mfma_kernel<HD, NT>), dim3(B * qblocks * H), dim3(256), 0, cur_stream(),
-                       (const unsigned short*)q.data_ptr(), (const unsigned short*)kp.data_ptr(),
-                       (const unsigned short*)vp.data_ptr(), (unsigned short*)out.data_ptr(),
-                       B, S, H, KVH, T32, (int)start_pos, q.stride(0), q.stride(1), scale,
-                       (float)softcap, (int)window);
+    dispatch_bool(fp8, [&](auto f8) {
+      if constexpr (decltype(f8)::value)
+        hipLaunchKernelGGL((attn_prefill_mfma_kv8_kernel<HD, NT>), dim3(B * qblocks * H), dim3(256), 0, cur_stream(),
+                           (const unsigned short*)q.data_ptr(), pc.kp8, pc.vp8, skp, svp,
+                           (unsigned short*)out.data_ptr(),
+                           B, S, H, KVH, T32, (int)start_pos, q.stride(0), q.stride(1), scale,
+                           (float)softcap, (int)window);
+      else
+        hipLaunchKernelGGL((attn_prefill_mfma_kernel<HD, NT>), dim3(B * qblocks * H), dim3(256), 0, cur_stream(),
+                           (const unsigned short*)q.data_ptr(), pc.kp, pc.vp, (unsigned short*)out.data_ptr(),
+                           B, S, H, KVH, T32, (int)start_pos, q.stride(0), q.stride(1), scale,
+                           (float)softcap, (int)window);
+    });
   });
   return out;
 }
@@ -3961,9 +4240,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale") = 0.0, py::arg("softcap") = 0.0, py::arg("window") = 0,
         py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("attn_prefill_mfma", &attn_prefill_mfma,
-        "causal GQA prefill flash attention on matrix cores (packed cache, hd=128)",
+        "causal GQA prefill flash attention on matrix cores (packed cache, hd 128 or 256; bf16, or e4m3 with scales)",
         py::arg("q"), py::arg("kp"), py::arg("vp"), py::arg("start_pos"),
-        py::arg("scale") = 0.0, py::arg("softcap") = 0.0, py::arg("window") = 0);
+        py::arg("scale") = 0.0, py::arg("softcap") = 0.0, py::arg("window") = 0,
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("moe_route", &moe_route,
         "fused MoE router: softmax-topk (mode 0) / sigmoid+group-limited (mode 1)",
         py::arg("logits"), py::arg("bias") = py::none(), py::arg("k") = 2,

@@ -101,21 +101,26 @@ class RingPipeline:
     # The llama decoder with MFMA attention appends to and reads only the packed
     # cache copies, so its caches are built without the plain [B, KVH, T, hd]
     # tensors (XOT_KV_PLAIN=1 keeps them). ShardKVCache ignores plain=False where
-    # it allocates no bf16 GQA packed copies (CPU, XOT_MFMA_ATTN=0, fp8-KV, ..).
+    # it allocates no GQA packed copies that prefill can read (CPU, XOT_MFMA_ATTN=0,
+    # fp8-KV without XOT_FP8_KV_PREFILL=1, ..).
     packed_only = (isinstance(model, LlamaShardedModel) and self.cfg.n_heads // self.cfg.n_kv_heads <= 16
                    and os.getenv("XOT_KV_PLAIN", "0") != "1")
+    fp8_kv = os.getenv("XOT_FP8_KV", "0") == "1"
     self.kv_plain = not (packed_only and device == "cuda" and ops.gqa_packed_kv(self.cfg.head_dim, dtype)
-                         and os.getenv("XOT_FP8_KV", "0") != "1")
+                         and (not fp8_kv or ops.fp8_kv_prefill_enabled()))
     if device == "cuda":
       # decode-GEMM weight prepack (memory permitting; KV caches below still
       # need room — reserve their size + headroom before packing greedily)
-      per_pos = (self.M * 2 * shards[rank].get_layer_count() * mb_batch * self.cfg.n_kv_heads
-                 * self.cfg.head_dim * (2 if dtype == torch.bfloat16 else 4))
+      kv_heads_pos = self.M * 2 * shards[rank].get_layer_count() * mb_batch * self.cfg.n_kv_heads  # K and V
+      per_pos = kv_heads_pos * self.cfg.head_dim * (2 if dtype == torch.bfloat16 else 4)
       kv_bytes = per_pos * self.total_len if self.kv_plain else 0
       if ops.gqa_packed_kv(self.cfg.head_dim, dtype):
         # the MFMA-packed cache copies, at the capacity rounded up to 32: a
-        # second residency beside the plain tensors, the only one without them
-        kv_bytes += per_pos * ((self.total_len + 31) // 32 * 32)
+        # second residency beside the plain tensors, the only one without them.
+        # A packed-only fp8-KV cache is counted as what it holds: e4m3 bytes and
+        # one fp32 scale per (kv head, position) for K and for V
+        t32 = (self.total_len + 31) // 32 * 32
+        kv_bytes += kv_heads_pos * (self.cfg.head_dim + 4) * t32 if fp8_kv and not self.kv_plain else per_pos * t32
       torch.cuda.empty_cache()  # release init-time cached blocks so the
       # pack policy's mem_get_info reflects actually-usable HBM
       model.pack_decode_weights(reserve_bytes=kv_bytes + (24 << 30))
