@@ -20,15 +20,23 @@ def main():
   p.add_argument("--gamma", type=int, default=4)
   p.add_argument("--max-new", type=int, default=64)
   p.add_argument("--dtype", default=None, choices=["bf16", "fp32"])
+  p.add_argument("--prompt-len", type=int, default=64,
+                 help="prompt tokens: verify then runs behind a cache this long (XOT_ATTN_CHUNK=1 selects the chunk kernel)")
   args = p.parse_args()
   dev = "cuda" if torch.cuda.is_available() else "cpu"
   dt = torch.bfloat16 if dev == "cuda" else torch.float32
   if args.dtype:
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+  # caches sized for the prompt and everything generated behind it (whole 32-position tiles);
+  # the decoder caps this by the two configs, and a prompt that then does not fit is refused
+  need = args.prompt_len + max(args.max_new, 16) + args.gamma + 2
   sd = SpeculativeDecoder.from_model_ids(args.target, args.draft, device=dev, dtype=dt,
-                                         gamma=args.gamma)
+                                         gamma=args.gamma, max_seq=(need + 31) // 32 * 32)
+  if sd.max_seq < need:
+    sys.exit(f"--prompt-len {args.prompt_len} + --max-new {args.max_new} needs {need} cache positions, "
+             f"the models allow {sd.max_seq}")
   g = torch.Generator().manual_seed(5)
-  prompt = torch.randint(0, 32000, (1, 64), generator=g)
+  prompt = torch.randint(0, 32000, (1, args.prompt_len), generator=g)
   # warm + invariant check
   toks, stats = sd.generate(prompt, max_new=16)
   sd.reset()
@@ -47,7 +55,7 @@ def main():
     torch.cuda.synchronize()
   dt_plain = time.perf_counter() - t0
   assert toks == ref
-  print(f"spec({args.target}+{args.draft} gamma={args.gamma}): "
+  print(f"spec({args.target}+{args.draft} gamma={args.gamma} prompt {args.prompt_len}): "
         f"{len(toks)/dt_spec:.1f} tok/s, accept {stats.accept_rate:.2f} "
         f"({stats.accepted}/{stats.proposed} over {stats.rounds} rounds); "
         f"plain {len(ref)/dt_plain:.1f} tok/s; outputs identical "

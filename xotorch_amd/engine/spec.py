@@ -45,7 +45,8 @@ class SpecStats:
 
 
 class SpeculativeDecoder:
-  """Greedy speculative decoding over two full (unsharded) models."""
+  """Greedy speculative decoding over two full (unsharded) models.
+  XOT_ATTN_CHUNK=1 runs the target's gamma + 1 token verify on the split-KV chunk attention kernel."""
 
   def __init__(self, target: torch.nn.Module, draft: torch.nn.Module,
                target_cfg: ModelConfig, draft_cfg: ModelConfig,
@@ -92,6 +93,9 @@ class SpeculativeDecoder:
     dev = self.device
     prompt = prompt.to(dev)
     S = prompt.shape[1]
+    # the prefill appends S positions to both caches; the append kernels do not check the capacity
+    if S > self.max_seq:
+      raise ValueError(f"prompt of {S} tokens does not fit caches of max_seq={self.max_seq}")
     stats = SpecStats()
     # prefill both models; t_cur = target's first prediction
     t_logits = self._forward(self.target, self.t_cache, prompt, 0)
@@ -153,6 +157,8 @@ class SpeculativeDecoder:
     self.t_cache.reset()
     prompt = prompt.to(dev)
     S = prompt.shape[1]
+    if S > self.max_seq:
+      raise ValueError(f"prompt of {S} tokens does not fit caches of max_seq={self.max_seq}")
     logits = self._forward(self.target, self.t_cache, prompt, 0)
     cur = int(logits[0, -1].argmax())
     out = [cur]

@@ -153,11 +153,49 @@ def fp8_kv_prefill_enabled() -> bool:
   return os.getenv("XOT_FP8_KV_PREFILL", "0") == "1"
 
 
+def attn_chunk_enabled() -> bool:
+  """XOT_ATTN_CHUNK (default 0, read per call): attn_prefill sends a short
+  chunk (attn_chunk_fits) to the split-KV attn_chunk kernel, which reads a kv
+  head's K/V once for all its query heads and splits the cache length over
+  waves: speculative verify, the last chunk of a chunked prefill, a short
+  prompt behind a long prefix."""
+  return os.getenv("XOT_ATTN_CHUNK", "0") == "1"
+
+
+def attn_chunk_fits(S: int, H: int, KVH: int, hd: int) -> bool:
+  """Whether attn_chunk takes a chunk of S positions: its S * H / KVH query rows
+  per kv head are the MFMA rows of one wave, at most 64 at head dim 128 and 32
+  at 256: 128 fp32 accumulators per lane, which run one wave per SIMD (half of
+  that, two)."""
+  return hd in PACKED_HEAD_DIMS and S >= 1 and KVH > 0 and H % KVH == 0 and S * (H // KVH) <= (64 if hd == 128 else 32)
+
+
+def attn_chunk(q, kp, vp, q_start, scale=None, softcap: float = 0.0, window: int = 0,
+               k_scale=None, v_scale=None):
+  """Causal GQA attention of a short chunk q [B, S, H, hd] over the packed cache
+  copies: row s of sequence b sits at position q_start[b] + s and sees
+  [0, q_start[b] + s] (the last `window` of them under a window). q_start is an
+  int or an int32 device tensor [B]; the cache must already hold the chunk's
+  own K/V and q_start + S must not exceed its capacity. GPU only."""
+  if not isinstance(q_start, torch.Tensor):
+    q_start = torch.full((q.shape[0],), int(q_start), dtype=torch.int32, device=q.device)
+  return _gpu().attn_chunk_mfma(q, kp, vp, q_start, scale or 0.0, softcap, window, k_scale, v_scale)
+
+
 def attn_prefill(q, k_cache, v_cache, start_pos: int, s_len: int, kp=None, vp=None,
                  scale=None, softcap: float = 0.0, window: int = 0, k_scale=None, v_scale=None):
   """k_scale / v_scale: the fp8-KV cache's per-position scales [B, KVH, T32]."""
   if q.is_cuda and q.dtype == torch.bfloat16 and kp is not None and q.shape[3] in PACKED_HEAD_DIMS \
      and mfma_attn_enabled():
+    # XOT_ATTN_CHUNK=1: a short chunk goes to the split-KV chunk kernel. An fp8-KV cache is
+    # read from its e4m3 copies, as decode reads it, also where XOT_FP8_KV_PREFILL=0 keeps
+    # longer prefills on the plain bf16 tensors.
+    if attn_chunk_enabled() and attn_chunk_fits(q.shape[1], q.shape[2], kp.shape[1], q.shape[3]) \
+       and (kp.dtype == torch.bfloat16 or (kp.dtype == torch.uint8 and k_scale is not None and v_scale is not None)) \
+       and _use_hip(q):
+      bf16 = kp.dtype == torch.bfloat16
+      return attn_chunk(q, kp, vp, start_pos, scale, softcap, window,
+                        None if bf16 else k_scale, None if bf16 else v_scale)
     # causal flash-forward on matrix cores, streaming the MFMA-packed cache;
     # softcap/window run gemma2 semantics inside the same kernel
     if kp.dtype == torch.bfloat16 and _use_hip(q):

@@ -2204,6 +2204,267 @@ __global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_prefill_mfma_kv8
 }
 
 // ---------------------------------------------------------------------------
+// Split-KV MFMA attention of a short query chunk (HD = 128 or 256, causal,
+// GQA): a few query positions behind a long cache — speculative verify, the
+// last chunk of a chunked prefill, a short prompt behind a shared prefix.
+//
+// The prefill kernels give such a chunk one workgroup per q head, walking the
+// whole cache serially with a handful of live rows; the decode kernel has the
+// right split but one query position. This kernel sits between the two:
+//   rows    G = H / KVH. A (b, kv head) has R = S * G query rows, rho = s * G + g
+//           (s-major, so the causal limits of a 16-row tile are monotone), in
+//           NTQ = 1, 2 or 4 tiles of 16 MFMA rows. Rows >= R are clamped copies
+//           of row R - 1 on load and are never stored.
+//   split   one wave per (b, kv head, split), four per workgroup, no barrier.
+//           A wave walks its 32-position tiles once: each K fragment is loaded
+//           once and scores all NTQ row tiles, each V fragment once for all NTQ
+//           PV MFMAs, so the K/V bytes of a (b, kv head) are read once instead
+//           of G * ceil(S / 128) times. The next tile's K is requested before
+//           the PV MFMAs, as in the decode kernel.
+//   limits  row rho sees [lo, end): end = q_start[b] + rho / G + 1 and
+//           lo = max(0, end - window) under a window, else 0. q_start is a device
+//           tensor (capture-safe, per-sequence offsets). A lane keeps the 4 * NTQ
+//           ends of its rows. The sequence's live range [min lo, max end) is
+//           cut into nsplit chunks of whole tiles, one per wave (the split
+//           count comes from the capacity, the chunks from q_start, so a short
+//           context in a long cache still spreads over the waves). Inside its
+//           chunk every row tile takes every position
+//           tile: skipping one wave-uniformly puts the accumulators' MFMAs and
+//           rescale under a branch, which cost scratch in every instantiation.
+//   masked  a row can have a whole tile masked while its running maximum is
+//           still -inf (an early row in a later tile; any row in a split above
+//           its limit). That gives p = 0 and keeps the state, the prefill
+//           kernel's guard; such a row stores l = 0 and the merge ignores it.
+//   stale   positions from a row's end on hold later rows' data, or anything at
+//           all past q_start + S: their score is -inf before the maximum, so p
+//           is exactly 0, and 0 times a finite V (or V scale) adds exactly 0.
+//   KV8     e4m3 codes in the same fragment geometry, one byte per element:
+//           a lane's 8 codes become the bf16x8 operand in registers (exact),
+//           the K scale multiplies the fp32 score, the V scale is folded into
+//           P before its one rounding to bf16. q stays bf16; no running PV scale.
+//   out     nsplit == 1 writes normalised bf16 rows to out [B, S, H, hd];
+//           otherwise one fp32 (m, l, o[hd]) partial per (row, split) at row id
+//           (b * S + s) * H + head for attn_decode_merge<HD>.
+// Every K / V / scale read lies in [0, T32) of its own (b, kv head): the range
+// is cut to T32 even if the caller's q_start + S is not.
+// Built without the packed fp32 VALU forms, on force-inlined helpers only, like
+// the two kernels above. The accumulators are NTQ * HD / 4 fp32 per lane. Up
+// to 64 of them two waves per SIMD (256 registers each) are stated and hold
+// without scratch. At the accepted limits (NTQ * HD = 512, four instantiations: 128 accumulators, 64
+// VGPRs of Q, 32 or 64 of K) they do not: with Q and the rows' (m, l) parked in
+// per-wave LDS images and no K prefetch the compiler still reported 48 to 164 B
+// of scratch per lane, so those four state one wave per SIMD and keep
+// everything in registers (resource table in docs/KERNELS.md).
+// ---------------------------------------------------------------------------
+
+// raw fragment of the packed cache (bf16x8, or 8 e4m3 bytes) -> bf16 MFMA operand
+template <bool KV8>
+DEVINL bf16x8 chunk_operand(typename Frag<KV8>::T raw) {
+  if constexpr (KV8) {
+    const unsigned long u = (unsigned long)raw;
+    return __builtin_bit_cast(bf16x8, e4m3x8_to_bf16x8((unsigned int)u, (unsigned int)(u >> 32)));
+  } else {
+    return raw;
+  }
+}
+
+template <int NTQ, bool KV8, int HD>
+__global__ __launch_bounds__(256, NTQ * HD > 256 ? 1 : 2) MLA_PF_NO_PK_F32 void attn_chunk_mfma_kernel(
+    const unsigned short* __restrict__ q, const void* __restrict__ kp, const void* __restrict__ vp,
+    const int* __restrict__ q_start, const float* __restrict__ sk, const float* __restrict__ sv,
+    float* __restrict__ ws_o, float* __restrict__ ws_ml, unsigned short* __restrict__ out,
+    int B, int S, int H, int KVH, int T32, int nsplit,
+    long long q_bstride, long long q_sstride, float scale, float softcap, int window) {
+  static_assert(GQA_PACKED_HD(HD), "packed GQA cache: head_dim 128 or 256");
+  static_assert(NTQ == 1 || NTQ == 2 || NTQ == 4, "1, 2 or 4 row tiles of 16");
+  static_assert(NTQ * HD <= 512, "at most 128 fp32 accumulators per lane");
+  constexpr int NC = HD / 32, NG = GQA_VGROUPS(HD), KTILE = GQA_KTILE(HD);  // qk chunks, pv groups
+  using FT = typename Frag<KV8>::T;
+  using FE = typename Frag<KV8>::E;
+  // per wave: the P image, 16 rows x 32 positions at a 48-element stride, reused
+  // by the wave's row tiles in turn (a tile's fragment is read back before the
+  // next tile's stores; one wave's LDS operations complete in order)
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][16 * 48];
+
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int col = lane & 15, quad = lane >> 4;
+  const int wid = blockIdx.x * 4 + wv;
+  if (wid >= B * KVH * nsplit) return;  // no barrier below
+  const int split = wid % nsplit;
+  const int kvh = (wid / nsplit) % KVH;
+  const int b = wid / (nsplit * KVH);
+  const int G = H / KVH, R = S * G;
+  const int qs = q_start[b];
+
+  // this lane's rows (quad * 4 + r of every tile): exclusive ends
+  // (the ends as the rows' chunk positions s = rho / G < 64, four to a register)
+  unsigned int spk[NTQ];
+#pragma unroll
+  for (int tq = 0; tq < NTQ; ++tq) {
+    spk[tq] = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) spk[tq] |= (unsigned int)(min(tq * 16 + quad * 4 + r, R - 1) / G) << (8 * r);
+  }
+  // rows are s-major: row 0 has the lowest lo, row R - 1 the highest end
+  const int lo_min = (window > 0) ? max(0, qs + 1 - window) : 0, end_max = qs + S;
+  // the wave's positions: the sequence's live range [min lo, max end), cut to the
+  // capacity, in nsplit chunks of whole 32-position tiles. Split over what is
+  // live, not over the capacity: behind a preallocated cache a capacity split
+  // would leave most waves empty and one wave the whole range.
+  const int base = (lo_min >> 5) << 5, live_end = min(end_max, T32);
+  const int chunk = (((max(live_end - base, 0) + nsplit - 1) / nsplit + 31) >> 5) << 5;
+  const int w0 = base + split * chunk;
+  const int w1 = min(w0 + chunk, live_end);
+
+  // Q fragments A[row = lane & 15][k = quad * 8 + j] per tile and 32-dim chunk
+  bf16x8 qf[NTQ][NC];
+#pragma unroll
+  for (int tq = 0; tq < NTQ; ++tq) {
+    const int rho = min(tq * 16 + col, R - 1);
+    const unsigned short* qrow = q + (size_t)b * q_bstride + (size_t)(rho / G) * q_sstride
+                                 + (size_t)(kvh * G + rho % G) * HD + quad * 8;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) qf[tq][c] = frag_load<false>(qrow + c * 32);
+  }
+
+  float m[NTQ][4], lsum[NTQ][4];
+  floatx4 acco[NTQ][NG];
+#pragma unroll
+  for (int tq = 0; tq < NTQ; ++tq) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[tq][r] = -INFINITY; lsum[tq][r] = 0.f; }
+#pragma unroll
+    for (int g = 0; g < NG; ++g) acco[tq][g] = (floatx4)(0.f);
+  }
+
+  const size_t head = (size_t)(b * KVH + kvh);
+  const FE* khead = reinterpret_cast<const FE*>(kp) + head * (T32 >> 4) * KTILE + lane * 8;
+  const FE* vhead = reinterpret_cast<const FE*>(vp) + head * NG * (T32 >> 5) * FRAG + lane * 8;
+  const float* ks_row = KV8 ? sk + head * T32 : nullptr;
+  const float* vs_row = KV8 ? sv + head * T32 : nullptr;
+
+  // the 2 * NC K fragments (2 half-tiles x NC chunks) of the tile at t, as stored
+  FT kbuf[2 * NC];
+  auto load_k_tile = [&](int t) __attribute__((always_inline)) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        kbuf[h * NC + c] = frag_load_nt<KV8>(khead + (size_t)((t >> 4) + h) * KTILE + c * FRAG);
+  };
+  if (w0 < w1) load_k_tile(w0);
+
+  for (int t = w0; t < w1; t += 32) {
+    // this lane's two score columns: positions t + h * 16 + col
+    float ksc[2] = {1.f, 1.f}, vsc[2] = {1.f, 1.f};
+    if constexpr (KV8) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) { ksc[h] = ks_row[t + h * 16 + col]; vsc[h] = vs_row[t + h * 16 + col]; }
+    }
+    bf16x8 kb[2 * NC];
+#pragma unroll
+    for (int i = 0; i < 2 * NC; ++i) kb[i] = chunk_operand<KV8>(kbuf[i]);
+
+    bf16x8 pf[NTQ];
+#pragma unroll
+    for (int tq = 0; tq < NTQ; ++tq) {
+      floatx4 sc[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        sc[h] = (floatx4)(0.f);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) sc[h] = Frag<false>::mfma(qf[tq][c], kb[h * NC + c], sc[h]);
+      }
+      // scale (and K scale), softcap, then the row's own limits
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        // pos < end and pos >= end - window, with end = qs + s + 1 and d = pos - qs - 1
+        const int d = t + h * 16 + col - qs - 1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int s_r = (int)((spk[tq] >> (8 * r)) & 0xff);
+          bool ok = s_r > d;
+          if (window > 0) ok = ok && s_r <= d + window;
+          float s = sc[h][r] * scale * ksc[h];
+          if (softcap > 0.f) s = softcap * kv8_tanh(s * (1.f / softcap));
+          sc[h][r] = ok ? s : -INFINITY;
+        }
+      }
+      float rmax[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(sc[0][r], sc[1][r]);
+#pragma unroll
+      for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(rmax[r], mla_pf_lane_xor(rmax[r], lane, mm));
+      float alpha[4], rsum[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float mn = fmaxf(m[tq][r], rmax[r]);
+        // nothing visible to this row yet: p = 0, state kept
+        if (mn == -INFINITY) { alpha[r] = 1.f; rsum[r] = 0.f; sc[0][r] = 0.f; sc[1][r] = 0.f; continue; }
+        alpha[r] = (lsum[tq][r] > 0.f) ? __expf(m[tq][r] - mn) : 0.f;
+        m[tq][r] = mn;
+        const float p0 = __expf(sc[0][r] - mn);
+        const float p1 = __expf(sc[1][r] - mn);
+        sc[0][r] = p0;
+        sc[1][r] = p1;
+        rsum[r] = p0 + p1;
+      }
+#pragma unroll
+      for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rsum[r] += mla_pf_lane_xor(rsum[r], lane, mm);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) lsum[tq][r] = lsum[tq][r] * alpha[r] + rsum[r];
+      attn_rescale(acco[tq], alpha, 1.f);
+      unsigned short* pl = plds_all[wv];
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          pl[(quad * 4 + r) * 48 + h * 16 + col] = f2b(sc[h][r] * vsc[h]);
+      pf[tq] = *reinterpret_cast<const bf16x8*>(pl + col * 48 + quad * 8);
+    }
+    // the next tile's K stream completes under the PV MFMAs
+    if (t + 32 < w1) load_k_tile(t + 32);
+    // ---- PV: out[tq][16 rows][g * 16 ..] += P[tq] x V, each V fragment loaded once ----
+    const FE* vt = vhead + (size_t)(t >> 5) * FRAG;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const bf16x8 vb = chunk_operand<KV8>(frag_load_nt<KV8>(vt + (size_t)g * (T32 >> 5) * FRAG));
+#pragma unroll
+      for (int tq = 0; tq < NTQ; ++tq)
+        acco[tq][g] = Frag<false>::mfma(pf[tq], vb, acco[tq][g]);
+    }
+  }
+
+  // ---- epilogue: final bf16 rows, or one (m, l, o[HD]) partial per (row, split) ----
+#pragma unroll
+  for (int tq = 0; tq < NTQ; ++tq) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rho = tq * 16 + quad * 4 + r;
+      if (rho >= R) continue;
+      const size_t row = ((size_t)b * S + rho / G) * H + kvh * G + rho % G;  // of out [B, S, H, hd]
+      if (nsplit == 1) {
+        const float inv = (lsum[tq][r] > 0.f) ? 1.f / lsum[tq][r] : 0.f;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) out[row * HD + g * 16 + col] = f2b(acco[tq][g][r] * inv);
+      } else {
+        const size_t pidx = row * nsplit + split;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) ws_o[pidx * HD + g * 16 + col] = acco[tq][g][r];
+        if (col == 0) {
+          ws_ml[pidx * 2 + 0] = m[tq][r];
+          ws_ml[pidx * 2 + 1] = lsum[tq][r];
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // SwiGLU: silu(gate) * up, elementwise, vectorized
 // ---------------------------------------------------------------------------
 
@@ -3469,6 +3730,96 @@ torch::Tensor attn_prefill_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor
   return out;
 }
 
+// KV splits of attn_chunk_mfma over a cache of capacity T32. The rule is the
+// decode launcher's (about 2048 waves, chunks of at least 32 positions, at most
+// 32 splits): it was tuned for attn_decode_mfma_kernel, not for this kernel,
+// whose waves carry up to four row tiles; docs/PERF.md has the sweep.
+// XOT_ATTN_CHUNK_NSPLIT (a power of two <= 32, read per call) overrides it for
+// measurement; chunks stay whole 32-position tiles either way.
+int64_t attn_chunk_nsplit(int64_t B, int64_t KVH, int64_t T32) {
+  if (const char* e = getenv("XOT_ATTN_CHUNK_NSPLIT")) {
+    const int v = atoi(e);
+    TORCH_CHECK(v >= 1 && v <= 32 && (v & (v - 1)) == 0,
+                "XOT_ATTN_CHUNK_NSPLIT must be a power of two <= 32, got ", e);
+    return v;
+  }
+  int64_t nsplit = 1;
+  while (B * KVH * nsplit * 2 < 4096 && (T32 / (nsplit * 2)) >= 32 && nsplit < 32) nsplit *= 2;
+  return nsplit;
+}
+
+// most query rows (S * H / KVH) of one (b, kv head) that attn_chunk_mfma takes
+constexpr int ATTN_CHUNK_MAX_ROWS(int hd) { return hd > 128 ? 32 : 64; }
+
+// Causal GQA attention of a short chunk q [B, S, H, hd] (hd 128 or 256; strided
+// over b / s, head rows contiguous) whose row s of sequence b sits at position
+// q_start[b] + s, over the packed cache copies (bf16, or e4m3 bytes with
+// k_scale / v_scale [B, KVH, T32]) that already hold positions
+// [0, q_start[b] + S). q_start is a device tensor, so the launch cannot check
+// q_start[b] + S <= T32 without a sync: the caller guarantees it, as seq_lens is
+// trusted by the decode kernels (the kernel reads nothing beyond T32 regardless).
+torch::Tensor attn_chunk_mfma(torch::Tensor q, torch::Tensor kp, torch::Tensor vp, torch::Tensor q_start,
+                              double scale_in, double softcap, int64_t window,
+                              c10::optional<torch::Tensor> k_scale,
+                              c10::optional<torch::Tensor> v_scale) {
+  CHK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.dim() == 4);
+  CHK(q.stride(3) == 1 && q.stride(2) == q.size(3));
+  const int B = q.size(0), S = q.size(1), H = q.size(2), hd = q.size(3);
+  CHK(q_start.is_cuda() && q_start.dtype() == torch::kInt32 && q_start.is_contiguous() && q_start.numel() == B);
+  TORCH_CHECK(GQA_PACKED_HD(hd), "attn_chunk_mfma: head_dim must be 128 or 256, got ", hd);
+  const bool fp8 = kp.dtype() == torch::kUInt8;
+  TORCH_CHECK((fp8 || kp.dtype() == torch::kBFloat16) && vp.dtype() == kp.dtype(),
+              "attn_chunk_mfma: packed cache copies are bf16, or e4m3 bytes in uint8 tensors");
+  TORCH_CHECK(fp8 == k_scale.has_value() && fp8 == v_scale.has_value(),
+              "attn_chunk_mfma: e4m3 (uint8) packed copies come with k_scale and v_scale, bf16 copies without");
+  check_packed_gqa_shapes("attn_chunk_mfma", kp, vp, hd);
+  CHK(kp.is_cuda() && vp.is_cuda() && kp.is_contiguous() && vp.is_contiguous());
+  const int KVH = kp.size(1);
+  const int T32 = kp.size(2) * 16;
+  TORCH_CHECK(kp.size(0) >= B && vp.size(0) == kp.size(0) && vp.size(1) == KVH && H % KVH == 0,
+              "attn_chunk_mfma: q [", B, ", ", S, ", ", H, ", ", hd, "] does not match the cache's batch ",
+              kp.size(0), " and kv heads ", KVH, " (H must be a multiple of KVH)");
+  const int R = S * (H / KVH);
+  TORCH_CHECK(S >= 1 && R <= ATTN_CHUNK_MAX_ROWS(hd),
+              "attn_chunk_mfma: S * H / KVH query rows per kv head must be <= 64 at head_dim 128 and <= 32 at 256, got ",
+              R, " at head_dim ", hd);
+  const float* skp = nullptr;
+  const float* svp = nullptr;
+  if (fp8) {
+    skp = fp8_scale_ptr(k_scale);
+    svp = fp8_scale_ptr(v_scale);
+    for (const auto* s : {&*k_scale, &*v_scale})
+      TORCH_CHECK(s->is_cuda() && s->dim() == 3 && s->size(0) == kp.size(0) && s->size(1) == KVH && s->size(2) == T32,
+                  "attn_chunk_mfma: k_scale / v_scale must be [B, KVH, T32] = [", kp.size(0), ", ", KVH, ", ", T32, "]");
+  }
+  const int nsplit = (int)attn_chunk_nsplit(B, KVH, T32);
+  const SplitKV kv(q, {(int64_t)B, (int64_t)S, (int64_t)H, (int64_t)hd}, B * S * H, nsplit, hd, nsplit > 1);
+  const float scale = (scale_in > 0.0) ? (float)scale_in : 1.0f / sqrtf((float)hd);
+  auto stream = cur_stream();
+  const int waves = B * KVH * nsplit;
+  auto launch = [&](auto ntq, auto f8, auto hdc) {
+    constexpr int NTQ = decltype(ntq)::value, HD = decltype(hdc)::value;
+    if constexpr (NTQ * 16 <= ATTN_CHUNK_MAX_ROWS(HD))
+      hipLaunchKernelGGL((attn_chunk_mfma_kernel<NTQ, decltype(f8)::value, HD>), dim3((waves + 3) / 4), dim3(256), 0,
+                         stream, (const unsigned short*)q.data_ptr(), (const void*)kp.data_ptr(),
+                         (const void*)vp.data_ptr(), q_start.data_ptr<int>(), skp, svp, kv.o(), kv.ml(),
+                         (unsigned short*)kv.out.data_ptr(), B, S, H, KVH, T32, nsplit,
+                         (long long)q.stride(0), (long long)q.stride(1), scale, (float)softcap, (int)window);
+    else
+      TORCH_CHECK(false, "attn_chunk_mfma: no kernel for ", NTQ, " row tiles at head_dim ", HD);
+  };
+  dispatch_packed_hd(hd, "attn_chunk_mfma", [&](auto hdc) {
+    dispatch_bool(fp8, [&](auto f8) {
+      switch ((R + 15) / 16) {  // row tiles; 3 run as 4
+        case 1: launch(IntC<1>{}, f8, hdc); break;
+        case 2: launch(IntC<2>{}, f8, hdc); break;
+        default: launch(IntC<4>{}, f8, hdc); break;
+      }
+    });
+  });
+  return nsplit > 1 ? kv.merge(stream) : kv.out;
+}
+
 // logits: [T, E] fp32 gate output -> (idx int32 [T,k], w fp32 [T,k]).
 std::vector<torch::Tensor> moe_route(torch::Tensor logits, c10::optional<torch::Tensor> bias,
                                      int64_t k, int64_t mode, int64_t n_group,
@@ -4244,6 +4595,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("kp"), py::arg("vp"), py::arg("start_pos"),
         py::arg("scale") = 0.0, py::arg("softcap") = 0.0, py::arg("window") = 0,
         py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+  m.def("attn_chunk_mfma", &attn_chunk_mfma,
+        "causal GQA attention of a short query chunk at per-sequence offsets, split over the KV length "
+        "(packed cache, hd 128 or 256; bf16, or e4m3 with scales; S * H / KVH <= 64 rows at hd 128, 32 at 256)",
+        py::arg("q"), py::arg("kp"), py::arg("vp"), py::arg("q_start"),
+        py::arg("scale") = 0.0, py::arg("softcap") = 0.0, py::arg("window") = 0,
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+  m.def("attn_chunk_nsplit", &attn_chunk_nsplit,
+        "KV splits attn_chunk_mfma launches for (B, KVH, capacity T32); XOT_ATTN_CHUNK_NSPLIT overrides");
   m.def("moe_route", &moe_route,
         "fused MoE router: softmax-topk (mode 0) / sigmoid+group-limited (mode 1)",
         py::arg("logits"), py::arg("bias") = py::none(), py::arg("k") = 2,
