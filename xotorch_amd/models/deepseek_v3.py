@@ -128,6 +128,10 @@ class MLAttention(nn.Module):
         return self._decode_mfma(x, q, q_pass, kv, seq_lens, positions, cos, sin)
       if start_pos < 0:
         start_pos = int(positions.reshape(-1)[0])
+      if not torch.is_grad_enabled() and ops.mla_chunk_enabled() and kv.kp.dtype == torch.bfloat16 \
+         and (nope, rope_d, vd) == (128, 64, 128) and ops.attn_chunk_mla_fits(S, H):
+        # XOT_MLA_CHUNK=1: a short chunk behind the cache stays absorbed
+        return self._chunk_absorbed(x, q, q_pass, kv, start_pos, positions, cos, sin)
       q_rot = _rope(q_rot, *_rope_rows(cos, sin, positions, B, S), cfg.rope_interleave)
       if not torch.is_grad_enabled():
         # GPU prefill: the attn_prefill_mla kernel, or query-chunked bf16
@@ -210,6 +214,32 @@ class MLAttention(nn.Module):
     out = out.permute(0, 2, 1, 3).reshape(B, S, H * vd)
     return self.o_proj(out)
 
+  def _absorb_kv_b(self):
+    """kv_b_proj split per head into the two absorbed factors (once)."""
+    if not hasattr(self, "_w_k"):
+      cfg = self.cfg
+      nope, vd = cfg.qk_nope_head_dim, cfg.v_head_dim
+      W = self.kv_b_proj.weight.view(cfg.n_heads, nope + vd, cfg.kv_lora_rank)
+      self._w_k = W[:, :nope, :].contiguous()   # [H, nope, lat]
+      self._w_v = W[:, nope:, :].contiguous()   # [H, vd, lat]
+
+  def _chunk_absorbed(self, x, q_raw, q_pass, kv, start_pos: int, positions, cos, sin):
+    """Absorbed attention of a short chunk behind the cache (XOT_MLA_CHUNK=1,
+    bf16 packed latent cache, dims 128 / 64 / 128, ops.attn_chunk_mla_fits):
+    _decode_mfma with S positions per sequence. kv_b is folded into q and out,
+    so nothing of the cache is expanded: hip_ops.hip attn_chunk_mla reads the
+    1152 B/token latent stream once per 64 query rows."""
+    cfg = self.cfg
+    B, S, H = q_pass.shape[0], q_pass.shape[1], cfg.n_heads
+    self._absorb_kv_b()
+    q_lat = torch.einsum("bshn,hnl->bshl", q_pass.to(x.dtype), self._w_k)
+    qf = ops.mla_q_prep(q_raw.contiguous(), q_lat.contiguous(), cos, sin,
+                        positions.to(torch.int32).contiguous(),
+                        cfg.qk_nope_head_dim, cfg.rope_interleave, False)[0]
+    out_lat = ops.attn_chunk_mla(qf.view(B, S, H, -1), kv.kp, kv.vp, start_pos, self.scale)
+    out = torch.einsum("bshl,hdl->bshd", out_lat, self._w_v).to(x.dtype)
+    return self.o_proj(out.reshape(B, S, H * cfg.v_head_dim))
+
   def _decode_mfma(self, x, q_raw, q_pass, kv, seq_lens, positions, cos, sin):
     """Absorbed-latent MFMA decode: kv_b is folded into q and out, so
     attention runs as MQA over the packed 1152 B/token latent stream
@@ -217,11 +247,8 @@ class MLAttention(nn.Module):
     kernel (mla_q_prep)."""
     cfg = self.cfg
     B, S, H = q_pass.shape[0], q_pass.shape[1], cfg.n_heads
-    nope, vd, lat = cfg.qk_nope_head_dim, cfg.v_head_dim, cfg.kv_lora_rank
-    if not hasattr(self, "_w_k"):
-      W = self.kv_b_proj.weight.view(H, nope + vd, lat)
-      self._w_k = W[:, :nope, :].contiguous()   # [H, nope, lat]
-      self._w_v = W[:, nope:, :].contiguous()   # [H, vd, lat]
+    nope, vd = cfg.qk_nope_head_dim, cfg.v_head_dim
+    self._absorb_kv_b()
     q_lat = torch.einsum("bshn,hnl->bshl", q_pass.to(x.dtype), self._w_k)
     fp8 = kv.kp.dtype == torch.uint8
     prep = ops.mla_q_prep(q_raw.contiguous(), q_lat.contiguous(), cos, sin,

@@ -306,7 +306,8 @@ moe_combine = _binding("moe_combine")  # (y [E*C, D], inv_pos, weights fp32) -> 
 # MLA (models/deepseek_v3.py) on the latent cache's packed copies (kp, vp; e4m3 with k_scale in fp8-KV mode)
 # (ckv, latent norm w, cos, sin, int32 positions, lat_c, rot_c, kp, vp, eps, interleave, k_scale | None): norm + rope + append
 mla_prep_append = _binding("mla_prep_append")
-# (q [B,S,H,qk], q_lat, cos, sin, int32 positions, nope, interleave, fp8) -> (q [B,H,576][, per-head scales when fp8])
+# (q [B,S,H,qk], q_lat [B,S,H,512], cos, sin, int32 positions [S] | [B*S], nope, interleave, fp8) ->
+# (q [B,H,576][, per-head scales when fp8]) at S = 1, (q [B,S,H,576],) bf16 above
 mla_q_prep = _binding("mla_q_prep")
 attn_decode_mla = _binding("attn_decode_mla")  # (q, kp, vp, seq_lens, scale, q_scale | None, k_scale | None) -> [B, H, lat]
 # causal flash prefill, nope 128 / rope 64 / v 128: (q [B,S,H,192], kvx [B,T,H,256] = the kv_b_proj output read in
@@ -318,6 +319,35 @@ def mla_prefill_enabled() -> bool:
   """XOT_MLA_PREFILL (default 1, read per call): MLA prefill attention on the
   attn_prefill_mla kernel; 0 keeps the query-chunked torch matmuls."""
   return os.getenv("XOT_MLA_PREFILL", "1") == "1"
+
+
+def mla_chunk_enabled() -> bool:
+  """XOT_MLA_CHUNK (default 0, read per call): a short DeepSeek chunk behind a
+  cache (attn_chunk_mla_fits: speculative verify, the last chunk of a chunked
+  prefill, a short follow-up turn) runs absorbed on attn_chunk_mla over the
+  packed latent cache instead of expanding the whole cache through kv_b_proj."""
+  return os.getenv("XOT_MLA_CHUNK", "0") == "1"
+
+
+def attn_chunk_mla_fits(S: int, H: int) -> bool:
+  """Whether attn_chunk_mla takes a chunk of S positions at H heads: at most
+  1024 query rows (64 row tiles of 16) per sequence, S = 8 at H = 128. A launch
+  limit, not a measured crossover with the prefill route."""
+  return S >= 1 and H >= 1 and S * H <= 1024
+
+
+def attn_chunk_mla(q, kp, vp, q_start, scale=None):
+  """Causal absorbed MLA attention of a short chunk: q [B, S, H, 576] bf16 (what
+  mla_q_prep returns) over the bf16 packed latent cache copies; row s of
+  sequence b sits at position q_start[b] + s and sees [0, q_start[b] + s].
+  q_start is an int (checked against the capacity) or an int32 device tensor
+  [B]; the cache must already hold the chunk's own latent rows. Returns
+  out_lat [B, S, H, 512]. GPU only."""
+  host_start = -1
+  if not isinstance(q_start, torch.Tensor):
+    host_start = int(q_start)
+    q_start = torch.full((q.shape[0],), host_start, dtype=torch.int32, device=q.device)
+  return _gpu().attn_chunk_mla(q, kp, vp, q_start, scale or 0.0, host_start)
 
 
 def _packed_epilogue(fn, x, wp, N, bias, epilogue):

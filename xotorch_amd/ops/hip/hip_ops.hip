@@ -1464,20 +1464,21 @@ __global__ __launch_bounds__(256) void mla_prep_append_kernel(
 }
 
 // q-side finisher: rope the 64-dim query tail and assemble the absorbed
-// query [B, H, 576] = [q_lat(512) | rope(q_rot)(64)] in one launch
+// query [B, S, H, 576] = [q_lat(512) | rope(q_rot)(64)] in one launch
 // (replaces ~6 torch ops per layer: rope mul/cat x2, cat, contiguous).
-// One wave per (b, h): q strided [B, S=1, H, 192], q_lat [B, 1, H, 512].
+// One wave per (b, s, h): q [B, S, H, nope + 64], q_lat [B, S, H, 512], both
+// contiguous; row b * S + s is roped at row_position (S = 1: decode).
 __global__ __launch_bounds__(256) void mla_q_prep_kernel(
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ q_lat,
     const float* __restrict__ cosb, const float* __restrict__ sinb,
     const int* __restrict__ positions, unsigned short* __restrict__ qfull,
-    int B, int H, long long q_bstride, int nope, int interleave, int npos,
+    int B, int S, int H, long long q_bstride, int nope, int interleave, int npos,
     unsigned char* __restrict__ q8, float* __restrict__ sq) {
   const int wid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (wid >= B * H) return;
+  if (wid >= B * S * H) return;
   const int lane = threadIdx.x & 63;
   const int h = wid % H;
-  const int b = wid / H;
+  const int b = wid / H;  // the row b * S + s
   const unsigned short* lsrc = q_lat + ((size_t)b * H + h) * MLA_LAT;
   float lv[8];
 #pragma unroll
@@ -1485,7 +1486,7 @@ __global__ __launch_bounds__(256) void mla_q_prep_kernel(
   float r1 = 0.f, r2 = 0.f;
   if (lane < 32)
     mla_rope_pair(q + (size_t)b * q_bstride + (size_t)h * (nope + MLA_ROPE) + nope, cosb, sinb,
-                  row_position(positions, npos, B, 1, b), lane, interleave, r1, r2);
+                  row_position(positions, npos, B, S, b), lane, interleave, r1, r2);
   if (q8 == nullptr) {
     unsigned short* dst = qfull + ((size_t)b * H + h) * MLA_DQK;
 #pragma unroll
@@ -2459,6 +2460,253 @@ __global__ __launch_bounds__(256, NTQ * HD > 256 ? 1 : 2) MLA_PF_NO_PK_F32 void 
           ws_ml[pidx * 2 + 0] = m[tq][r];
           ws_ml[pidx * 2 + 1] = lsum[tq][r];
         }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Absorbed MLA attention of a short query chunk (DeepSeek speculative verify,
+// the last chunk of a chunked prefill, a short turn behind a long prefix):
+// q [B, S, H, 576] (absorbed latent 512 | roped tail 64) over the packed latent
+// cache, row s of sequence b at position q_start[b] + s. Causal, no window, no
+// softcap. attn_decode_mla_kernel with more than one position per sequence,
+// and a different split of the work:
+//   rows    a sequence has R = S * H rows, rho = s * H + h (s-major, the order
+//           of q and out), in NRT = ceil(R / 16) row tiles. A tile may straddle
+//           two values of s (H = 20) and the last may be partial: rows >= R are
+//           clamped to R - 1 on load and never stored. Row rho sees
+//           [0, q_start[b] + rho / H + 1); a lane keeps the 4 chunk positions
+//           rho / H of its rows.
+//   split   one row tile is 16 x 512 fp32 = 128 accumulators per lane, so a
+//           wave owns ONE row tile (one wave per SIMD, as 128 accumulators run
+//           in attn_chunk_mfma_kernel) and the 18 Q fragments stay in registers.
+//           A 4-wave workgroup takes 4 consecutive row tiles of one (b, split)
+//           and stages each 32-position tile of the latent+rope image ONCE in
+//           LDS for all four: the 36 KB of a (b, tile) leave L2 once per 64
+//           rows. Grid B x ceil(NRT / 4) x nsplit. A wave whose row tile is
+//           past NRT (the second workgroup at H = 16, S = 5 has one live wave)
+//           still stages, computes on clamped rows and reaches every barrier;
+//           it stores nothing.
+//   stage   two consecutive 16-position K tiles of kp are 36864 contiguous
+//           bytes: 9 coalesced 16 B loads per thread, issued before this tile's
+//           MFMAs and parked in the other LDS buffer after them, one barrier
+//           per tile (attn_prefill_mla_kernel's double buffer). 2 x 36 KB + four
+//           P images = 78 KB; the registers already hold a CU to one workgroup.
+//   K = V   absorbed V is the first 512 dims of K, so the PV operand comes from
+//           the SAME staged tile through the transposing LDS read
+//           (ds_read_b64_tr_b16, as attn_prefill_mla_kernel reads its V) and vp
+//           is not read at all: 1152 B per token instead of 2176.
+//   layout  position-major rows of 72 16-byte pieces, dense (1152 B = 8 mod 16
+//           pieces), piece e of row p stored at piece e ^ swz(p), swz(p) =
+//           2 * ((p >> 1) & 3) | ((p >> 3) & 1) < 8. Counted on 64 banks = 16
+//           pieces: a score b128 read (16 lanes, one e, rows 0..15) meets the 8
+//           even rows on 8 distinct pieces of one half and the odd rows on the
+//           other half; a transposing b64 read (32 lanes, 8 consecutive rows,
+//           the piece pair 2g, 2g + 1) meets 4 even rows on 4 distinct pairs of
+//           one half and the odd rows on the other. Both conflict-free by count;
+//           docs/KERNELS.md has what the LDS bank-conflict counter showed.
+//   scores  18 v_mfma_f32_16x16x32_bf16 per half-tile, fp32 online softmax with
+//           the row's own limit, P rounded once to bf16 through the wave's P
+//           image, 32 PV MFMAs per tile.
+//   masked  / stale: as attn_chunk_mfma_kernel. A position from a row's limit
+//           on (a later row's data, or anything at all past q_start + S) scores
+//           -inf by select before the maximum: p is exactly 0, and 0 times a
+//           finite value adds 0. A row with a whole tile masked while its
+//           maximum is still -inf keeps its state; in a split above its limit it
+//           stores l = 0, which attn_decode_merge ignores.
+//   range   the live range [0, max end) of the sequence, not the capacity, is
+//           cut into nsplit chunks of whole tiles; a workgroup stops at its own
+//           last row's end. Every global read is a whole tile below
+//           ceil(min(q_start + S, T32) / 32) * 32 <= T32 of its own sequence.
+//   out     nsplit == 1 writes normalised bf16 rows to out [B, S, H, 512];
+//           otherwise fp32 (m, l, o[512]) partials at row id b * R + rho =
+//           (b * S + s) * H + h for attn_decode_merge<512>.
+// Built without the packed fp32 VALU forms, on force-inlined helpers only, with
+// its own softmax and P-image lines, like the kernels above.
+// ---------------------------------------------------------------------------
+
+constexpr int MLA_CK_MAX_ROWS = 1024;          // launch limit on R = S * H: 64 row tiles
+constexpr int MLA_CK_STAGE = 32 * MLA_DQK;     // elements of a staged 32-position tile
+constexpr int MLA_CK_LOADS = MLA_CK_STAGE / 8 / 256;  // 16 B pieces per thread and tile
+
+// piece swizzle of staged row p (bit 4 of p, the half-tile, does not enter)
+DEVINL int mla_ck_swz(int p) { return (((p >> 1) & 3) << 1) | ((p >> 3) & 1); }
+
+__global__ __launch_bounds__(256, 1) MLA_PF_NO_PK_F32 void attn_chunk_mla_kernel(
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ kp,
+    const int* __restrict__ q_start, float* __restrict__ ws_o, float* __restrict__ ws_ml,
+    unsigned short* __restrict__ out, int B, int S, int H, int T32, int nsplit, float scale) {
+  static_assert(MLA_CK_LOADS * 256 * 8 == MLA_CK_STAGE && MLA_DQK % 64 == 0, "whole pieces, swizzle inside a row");
+  __shared__ __attribute__((aligned(16))) unsigned short kv_lds[2][MLA_CK_STAGE];
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][16 * 48];
+
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  const int col = lane & 15, quad = lane >> 4;
+  const int R = S * H, nrt = (R + 15) >> 4, nwg = (nrt + 3) >> 2;
+  // block -> (b, workgroup of 4 row tiles, split): splits fastest
+  const int split = blockIdx.x % nsplit;
+  const int wg = (blockIdx.x / nsplit) % nwg;
+  const int b = blockIdx.x / (nsplit * nwg);
+  const int rt = wg * 4 + wv;  // this wave's row tile; >= nrt: no real row
+  const int qs = q_start[b];
+
+  // the workgroup's positions (the same for its four waves: every barrier below
+  // is reached by all of them): this split's chunk of the sequence's live range,
+  // cut at the end of the workgroup's last row
+  const int live_end = min(qs + S, T32);
+  const int chunk = (((live_end + nsplit - 1) / nsplit + 31) >> 5) << 5;
+  const int w0 = split * chunk;
+  const int w1 = min(min(w0 + chunk, live_end), qs + min(wg * 64 + 63, R - 1) / H + 1);
+
+  // this lane's rows (quad * 4 + r of the tile): chunk positions s = rho / H
+  int srow[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) srow[r] = min(rt * 16 + quad * 4 + r, R - 1) / H;
+
+  // Q fragments A[row = col][k = quad * 8 + j] of the 18 32-dim chunks
+  bf16x8 qf[MLA_CHQK];
+  {
+    const unsigned short* qrow = q + ((size_t)b * R + min(rt * 16 + col, R - 1)) * MLA_DQK + quad * 8;
+#pragma unroll
+    for (int c = 0; c < MLA_CHQK; ++c) qf[c] = frag_load<false>(qrow + c * 32);
+  }
+
+  float m[4], lsum[4];
+  floatx4 acco[MLA_GPV];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { m[r] = -INFINITY; lsum[r] = 0.f; }
+#pragma unroll
+  for (int g = 0; g < MLA_GPV; ++g) acco[g] = (floatx4)(0.f);
+
+  // staging: piece i = tid + 256 k of the tile's 2304, in the K image's order:
+  // half-tile i / 1152, then 32-dim chunk, then quarter, then position i & 15,
+  // so it is piece e = (i % 1152) >> 4 of row p = 16 (i / 1152) + (i & 15)
+  const unsigned short* kseq = kp + (size_t)b * (T32 >> 4) * MLA_KTILE + tid * 8;
+  const int st_swz = mla_ck_swz(tid & 15);
+  ushort8 st[MLA_CK_LOADS];
+  auto stage_load = [&](int t) __attribute__((always_inline)) {
+    const unsigned short* src = kseq + (size_t)(t >> 4) * MLA_KTILE;
+#pragma unroll
+    for (int k = 0; k < MLA_CK_LOADS; ++k) st[k] = *(const ushort8*)(src + k * 2048);
+  };
+  auto stage_store = [&](int buf) __attribute__((always_inline)) {
+    unsigned short* d = kv_lds[buf];
+#pragma unroll
+    for (int k = 0; k < MLA_CK_LOADS; ++k) {
+      const int i = tid + k * 256;
+      const int hh = i >= MLA_KTILE / 8 ? 1 : 0;
+      const int e = (i - hh * (MLA_KTILE / 8)) >> 4;
+      *(ushort8*)(d + (hh * 16 + (tid & 15)) * MLA_DQK + ((e ^ st_swz) << 3)) = st[k];
+    }
+  };
+
+  // score read: row hh * 16 + col, piece c * 4 + quad -> the odd chunks flip bit 2
+  const int kx0 = (quad ^ mla_ck_swz(col)) << 3, kx1 = kx0 ^ 32;
+  // PV read (ds_read_b64_tr_b16, lanes as in attn_prefill_mla_kernel): lane L of
+  // a 16-lane group points at 4 dims of row 4 quad + (L >> 2), dims
+  // g * 16 + 4 (L & 3): piece 2 g + ((L & 3) >> 1), its half L & 1
+  const int vrow_i = quad * 4 + (col >> 2);
+  const int vy = ((col & 3) >> 1) ^ mla_ck_swz(vrow_i);
+  unsigned short* pl = plds_all[wv];
+
+  if (w0 < w1) {
+    stage_load(w0);
+    stage_store(0);
+  }
+  mla_pf_barrier();
+
+  int buf = 0;
+  for (int t = w0; t < w1; t += 32, buf ^= 1) {
+    const bool more = t + 32 < w1;
+    if (more) stage_load(t + 32);  // in flight under this tile's MFMAs
+    const unsigned short* dk = kv_lds[buf];
+    floatx4 sc[2];
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      sc[hh] = (floatx4)(0.f);
+      const unsigned short* krow = dk + (hh * 16 + col) * MLA_DQK;
+#pragma unroll
+      for (int c = 0; c < MLA_CHQK; ++c) {
+        const bf16x8 kb = *reinterpret_cast<const bf16x8*>(krow + (c >> 1) * 64 + ((c & 1) ? kx1 : kx0));
+        sc[hh] = Frag<false>::mfma(qf[c], kb, sc[hh]);
+      }
+    }
+    // the row's own limit: pos < q_start + s + 1, d = pos - q_start - 1
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      const int d = t + hh * 16 + col - qs - 1;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sc[hh][r] = (srow[r] > d) ? sc[hh][r] * scale : -INFINITY;
+    }
+    float rmax[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(sc[0][r], sc[1][r]);
+#pragma unroll
+    for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(rmax[r], mla_pf_lane_xor(rmax[r], lane, mm));
+    float alpha[4], rsum[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float mn = fmaxf(m[r], rmax[r]);
+      // nothing visible to this row yet: p = 0, state kept
+      if (mn == -INFINITY) { alpha[r] = 1.f; rsum[r] = 0.f; sc[0][r] = 0.f; sc[1][r] = 0.f; continue; }
+      alpha[r] = (lsum[r] > 0.f) ? __expf(m[r] - mn) : 0.f;
+      m[r] = mn;
+      const float p0 = __expf(sc[0][r] - mn);
+      const float p1 = __expf(sc[1][r] - mn);
+      sc[0][r] = p0;
+      sc[1][r] = p1;
+      rsum[r] = p0 + p1;
+    }
+#pragma unroll
+    for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) rsum[r] += mla_pf_lane_xor(rsum[r], lane, mm);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) lsum[r] = lsum[r] * alpha[r] + rsum[r];
+    attn_rescale(acco, alpha, 1.f);
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        pl[(quad * 4 + r) * 48 + hh * 16 + col] = f2b(sc[hh][r]);
+    // P in the transposing read's contraction order: k = quad * 8 + j is position
+    // 4 quad + j for j < 4 and 16 + 4 quad + j - 4 above
+    const bf16x4 plo = *reinterpret_cast<const bf16x4*>(pl + col * 48 + quad * 4);
+    const bf16x4 phi = *reinterpret_cast<const bf16x4*>(pl + col * 48 + 16 + quad * 4);
+    const bf16x8 pf = __builtin_shufflevector(plo, phi, 0, 1, 2, 3, 4, 5, 6, 7);
+    const unsigned short* vrow = dk + vrow_i * MLA_DQK + (col & 1) * 4;
+#pragma unroll
+    for (int g = 0; g < MLA_GPV; ++g) {
+      const int off = (g >> 2) * 64 + ((((g & 3) * 2) ^ vy) << 3);
+      const v4i16 vlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(vrow + off));
+      const v4i16 vhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(vrow + 16 * MLA_DQK + off));
+      const v8i16 vb = __builtin_shufflevector(vlo, vhi, 0, 1, 2, 3, 4, 5, 6, 7);
+      acco[g] = Frag<false>::mfma(pf, __builtin_bit_cast(bf16x8, vb), acco[g]);
+    }
+    if (more) stage_store(buf ^ 1);  // last read before the previous barrier
+    mla_pf_barrier();
+  }
+
+  // ---- epilogue: final bf16 rows, or one (m, l, o[512]) partial per (row, split) ----
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int rho = rt * 16 + quad * 4 + r;
+    if (rho >= R) continue;
+    const size_t row = (size_t)b * R + rho;  // of out [B, S, H, 512]
+    if (nsplit == 1) {
+      const float inv = (lsum[r] > 0.f) ? 1.f / lsum[r] : 0.f;
+#pragma unroll
+      for (int g = 0; g < MLA_GPV; ++g) out[row * MLA_LAT + g * 16 + col] = f2b(acco[g][r] * inv);
+    } else {
+      const size_t pidx = row * nsplit + split;
+#pragma unroll
+      for (int g = 0; g < MLA_GPV; ++g) ws_o[pidx * MLA_LAT + g * 16 + col] = acco[g][r];
+      if (col == 0) {
+        ws_ml[pidx * 2 + 0] = m[r];
+        ws_ml[pidx * 2 + 1] = lsum[r];
       }
     }
   }
@@ -3877,30 +4125,35 @@ torch::Tensor moe_combine(torch::Tensor y, torch::Tensor inv_pos, torch::Tensor 
   return out;
 }
 
-// q: [B, 1, H, nope+64] bf16 contiguous (raw projections, nope part is the
-// un-roped passthrough); q_lat: [B, 1, H, 512] absorbed latent query;
-// returns qfull [B, H, 576] with the roped 64-dim tail appended.
+// q: [B, S, H, nope+64] bf16 contiguous (raw projections, nope part is the
+// un-roped passthrough); q_lat: [B, S, H, 512] absorbed latent query;
+// positions [S] or [B * S]. Returns qfull with the roped 64-dim tail appended:
+// [B, H, 576] at S = 1 (decode; e4m3 with per-head scales when fp8), else
+// [B, S, H, 576] bf16, the query of attn_chunk_mla.
 std::vector<torch::Tensor> mla_q_prep(torch::Tensor q, torch::Tensor q_lat, torch::Tensor cos,
                                       torch::Tensor sin, torch::Tensor positions,
                                       int64_t nope, bool interleave, bool fp8) {
   CHK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.is_contiguous());
   CHK(q_lat.is_cuda() && q_lat.dtype() == torch::kBFloat16 && q_lat.is_contiguous());
   CHK(positions.dtype() == torch::kInt32 && positions.is_contiguous());
-  const int B = q.size(0), H = q.size(2);
-  CHK(q.size(1) == 1 && q.size(3) == nope + MLA_ROPE);
-  CHK(q_lat.numel() == (long long)B * H * MLA_LAT);
+  CHK(q.dim() == 4);
+  const int B = q.size(0), S = q.size(1), H = q.size(2);
+  CHK(S >= 1 && q.size(3) == nope + MLA_ROPE);
+  TORCH_CHECK(S == 1 || !fp8, "mla_q_prep: the e4m3 query is the decode kernel's, one position per sequence");
+  CHK(q_lat.numel() == (long long)B * S * H * MLA_LAT);
   const int npos = (int)positions.numel();
-  CHK(npos == 1 || npos == B);
-  const int waves = B * H;
+  CHK(npos == S || npos == B * S);
+  const int waves = B * S * H;
   // bf16: {qfull}; fp8: {q8, one scale per (b, h)}
-  auto qout = torch::empty({(long)B, (long)H, (long)MLA_DQK},
-                           q.options().dtype(fp8 ? torch::kUInt8 : torch::kBFloat16));
+  auto qout = S == 1 ? torch::empty({(long)B, (long)H, (long)MLA_DQK},
+                                    q.options().dtype(fp8 ? torch::kUInt8 : torch::kBFloat16))
+                     : torch::empty({(long)B, (long)S, (long)H, (long)MLA_DQK}, q.options());
   torch::Tensor sq;
   if (fp8) sq = torch::empty({(long)B, (long)H}, q.options().dtype(torch::kFloat32));
   hipLaunchKernelGGL(mla_q_prep_kernel, dim3((waves + 3) / 4), dim3(256), 0, cur_stream(),
                      (const unsigned short*)q.data_ptr(), (const unsigned short*)q_lat.data_ptr(),
                      cos.data_ptr<float>(), sin.data_ptr<float>(), positions.data_ptr<int>(),
-                     fp8 ? nullptr : (unsigned short*)qout.data_ptr(), B, H,
+                     fp8 ? nullptr : (unsigned short*)qout.data_ptr(), B, S, H,
                      (long long)H * (nope + MLA_ROPE), (int)nope, interleave ? 1 : 0, npos,
                      fp8 ? (unsigned char*)qout.data_ptr() : nullptr,
                      fp8 ? sq.data_ptr<float>() : nullptr);
@@ -3995,6 +4248,71 @@ torch::Tensor attn_decode_mla(torch::Tensor q, torch::Tensor kp, torch::Tensor v
                        seq_lens.data_ptr<int>(), kv.o(), kv.ml(), B, H, T32, nsplit, scale, sqp, ksp);
   });
   return kv.merge(stream);
+}
+
+// KV splits of attn_chunk_mla (q [B, S, H, 576]) over a latent cache of `cap`
+// positions. The decode launcher's rule, counted in workgroups: one workgroup of
+// attn_chunk_mla_kernel fills a CU (one wave per SIMD, 78 KB of LDS), so double
+// the splits while the grid stays within two workgroups per CU (512) and a
+// chunk keeps at least one 32-position tile of the capacity, at most 32 splits.
+// A split costs 2 KB of fp32 partial per row, written and read back by the merge
+// (S * H rows: more than the whole latent stream once nsplit * S * H * 2 KB
+// passes it), so the rule stops earlier than the decode kernel's 4096 waves. Not
+// tuned: docs/PERF.md has the sweep. XOT_MLA_CHUNK_NSPLIT (a power of two <= 64,
+// read per call) overrides it for measurement.
+int64_t attn_chunk_mla_nsplit(int64_t B, int64_t H, int64_t S, int64_t cap) {
+  if (const char* e = getenv("XOT_MLA_CHUNK_NSPLIT")) {
+    const int v = atoi(e);
+    TORCH_CHECK(v >= 1 && v <= 64 && (v & (v - 1)) == 0,
+                "XOT_MLA_CHUNK_NSPLIT must be a power of two <= 64, got ", e);
+    return v;
+  }
+  const int64_t nwg = ((S * H + 15) / 16 + 3) / 4;
+  int64_t nsplit = 1;
+  while (B * nwg * nsplit * 2 <= 512 && (cap / (nsplit * 2)) >= 32 && nsplit < 32) nsplit *= 2;
+  return nsplit;
+}
+
+// Causal absorbed MLA attention of a short chunk: q [B, S, H, 576] bf16
+// contiguous (what mla_q_prep returns), row s of sequence b at position
+// q_start[b] + s, over the bf16 packed latent cache kp [B, T32/16, 18, 64, 8]
+// that already holds positions [0, q_start[b] + S). vp [B, 32, T32/32, 64, 8] is
+// the cache's other copy: checked, not read (V is the first 512 dims of K).
+// q_start is a device tensor, so q_start[b] + S <= T32 is the caller's word, as
+// for attn_chunk_mfma (the kernel reads nothing beyond T32 regardless);
+// host_start >= 0 is the same offset known on the host, and is checked.
+// Returns out_lat [B, S, H, 512] bf16.
+torch::Tensor attn_chunk_mla(torch::Tensor q, torch::Tensor kp, torch::Tensor vp, torch::Tensor q_start,
+                             double scale_in, int64_t host_start) {
+  CHK(q.is_cuda() && q.dim() == 4 && q.is_contiguous());
+  TORCH_CHECK(q.size(3) == MLA_DQK, "attn_chunk_mla: q is [B, S, H, 576] (absorbed latent 512 | rope 64), got last dim ",
+              q.size(3));
+  TORCH_CHECK(q.dtype() == torch::kBFloat16 && kp.dtype() == torch::kBFloat16 && vp.dtype() == torch::kBFloat16,
+              "attn_chunk_mla: bf16 q and bf16 packed latent cache only (the e4m3 cache keeps the prefill route)");
+  const int64_t B = q.size(0), S = q.size(1), H = q.size(2);
+  TORCH_CHECK(q_start.is_cuda() && q_start.dtype() == torch::kInt32 && q_start.is_contiguous() && q_start.numel() == B,
+              "attn_chunk_mla: q_start must be an int32 device tensor [B]");
+  CHK(kp.is_cuda() && vp.is_cuda() && kp.is_contiguous() && vp.is_contiguous());
+  TORCH_CHECK(kp.dim() == 5 && kp.size(0) >= B && kp.size(2) == MLA_CHQK && kp.size(3) == 64 && kp.size(4) == 8
+              && kp.size(1) % 2 == 0 && vp.dim() == 5 && vp.size(0) == kp.size(0) && vp.size(1) == MLA_GPV
+              && vp.size(2) * 2 == kp.size(1),
+              "attn_chunk_mla: kp [B, T32/16, 18, 64, 8] and vp [B, 32, T32/32, 64, 8] of one cache, T32 a multiple of 32");
+  const int64_t T32 = kp.size(1) * 16;
+  TORCH_CHECK(B >= 1 && S >= 1 && H >= 1 && S * H <= MLA_CK_MAX_ROWS,
+              "attn_chunk_mla: S * H query rows per sequence must be <= ", MLA_CK_MAX_ROWS, ", got ", S * H);
+  TORCH_CHECK(host_start < 0 || host_start + S <= T32,
+              "attn_chunk_mla: q_start + S = ", host_start + S, " exceeds the cache's capacity ", T32);
+  CHK((uintptr_t)q.data_ptr() % 16 == 0 && (uintptr_t)kp.data_ptr() % 16 == 0);
+  const int nsplit = (int)attn_chunk_mla_nsplit(B, H, S, T32);
+  const int64_t nwg = ((S * H + 15) / 16 + 3) / 4;
+  const SplitKV kv(q, {B, S, H, (int64_t)MLA_LAT}, (int)(B * S * H), nsplit, MLA_LAT, nsplit > 1);
+  const float scale = (scale_in > 0.0) ? (float)scale_in : 1.0f / sqrtf((float)MLA_DQK);
+  auto stream = cur_stream();
+  hipLaunchKernelGGL(attn_chunk_mla_kernel, dim3((unsigned)(B * nwg * nsplit)), dim3(256), 0, stream,
+                     (const unsigned short*)q.data_ptr(), (const unsigned short*)kp.data_ptr(),
+                     q_start.data_ptr<int>(), kv.o(), kv.ml(), (unsigned short*)kv.out.data_ptr(),
+                     (int)B, (int)S, (int)H, (int)T32, nsplit, scale);
+  return nsplit > 1 ? kv.merge(stream) : kv.out;
 }
 
 // q: [B, S, H, 192] bf16 (q_pass | roped q_rot; strided over b/s OK, head rows
@@ -4632,6 +4950,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MLA causal flash prefill (qk 192 = nope 128 | shared rope 64, v 128) on matrix cores, "
         "K/V read in place from the kv_b_proj output and the plain rope cache",
         py::arg("q"), py::arg("kvx"), py::arg("rot"), py::arg("start_pos"), py::arg("scale"));
+  m.def("attn_chunk_mla", &attn_chunk_mla,
+        "absorbed MLA attention of a short chunk q [B, S, H, 576] at q_start over the bf16 packed latent cache, "
+        "4 row tiles per workgroup on one LDS-staged tile stream, split over the live length",
+        py::arg("q"), py::arg("kp"), py::arg("vp"), py::arg("q_start"), py::arg("scale") = 0.0,
+        py::arg("host_start") = -1);
+  m.def("attn_chunk_mla_nsplit", &attn_chunk_mla_nsplit,
+        "KV splits attn_chunk_mla takes for q [B, S, H, 576] over a cache of `cap` positions");
   m.def("mfma16_probe", &mfma16_probe, "v_mfma_f32_16x16x32_bf16 layout probe (tests)");
   m.def("swiglu", &swiglu, "SwiGLU activation");
 }
