@@ -1,7 +1,10 @@
-"""fp64 oracle for the decode-attention kernels (plain helper module, not a
+"""fp64 oracle for the attention kernels (plain helper module, not a
 conftest): reference packers of the fragment layouts, seeded input families
 built to make wrong kernels visible, fp64 references with switchable
 mutations, a derived error bound, and a CPU emulator of the fp8 P quantization.
+The decode section comes first; the prefill section at the end of the file
+(`prefill_reference`, the one reference of the prefill, fp8-KV prefill and
+chunk tests) states the same bound in its bf16-P form.
 
 Everything here runs on the CPU. The GPU tests move `device_inputs(case)` to
 the card, launch one kernel and hand its output to `ratio(case, ref, out)`.
@@ -649,3 +652,309 @@ SPECS = _specs()
 # one zero-length row between two live ones, per kernel
 ZERO_SPECS = [Spec(f"zero-{s.name}", s.kernel, s.hd, s.fp8, s.H, s.KVH, 128, (40, 0, 97), families=("edges",))
               for s in SPECS if s.name.endswith("-T128") and s.H in (8, 16)]
+
+
+# ===========================================================================
+# Prefill attention (attn_prefill_mfma and the kernels copied from it): one
+# fp64 reference under the bf16-P bound above, seeded input families that make
+# an off-by-one visible at every row, the mutations a wrong kernel would
+# amount to, and a CPU emulator of the kernel's tile loop.
+#
+# The bound is the bf16-P form of the module docstring with Dk = hd and T the
+# number of cache positions handed in; a split-KV kernel adds its merge's
+# accumulations as extra_acc:
+#   eps_rel = 2 (2^-24 (hd + 8) sabs + 2^-22 + 2^-22 softcap) + 2^-24 (2 T + 16 + extra_acc)
+#   bound   = (2^-8 absw + eps_rel absw)(1 + 2^-8) + 2^-8 |ref|
+# ===========================================================================
+
+def prefill_reference(q, k, v, end, scale, softcap, window, extra_acc=0, *, end_shift=0, lo_shift=0, drop=None,
+                      scale_mul=1.0, no_softcap=False, kv_map=None):
+  """fp64 over q's bf16 values [B, S, H, hd] and the k / v [B, KVH, T, hd] the
+  kernel reads (bf16 rows or dequantised codes); row (b, s) sees
+  [max(0, end[b, s] - window), end[b, s]) -> (ref, bound), both [B, S, H, hd].
+  A row that sees nothing gives 0. Mutations, inside the reference only:
+  end_shift / lo_shift move the causal limit / the window start, drop =
+  (t0, t1) hides positions [t0, t1) (ints, or [S] tensors: a range per row),
+  scale_mul scales the scores, no_softcap skips the tanh, kv_map names the kv
+  head each q head reads."""
+  B, S, H, hd = q.shape
+  T, rep = k.shape[2], H // k.shape[1]
+  qd = q.double()
+  if kv_map is None:
+    kk, vv = k.repeat_interleave(rep, dim=1), v.repeat_interleave(rep, dim=1)
+  else:
+    kk, vv = k[:, list(kv_map)], v[:, list(kv_map)]
+  end = torch.as_tensor(end)[:, None, :, None]  # [B, 1, S, 1]
+  kpos = torch.arange(T)
+  masked = kpos >= end + end_shift
+  if window:
+    masked = masked | (kpos < end - window + lo_shift)
+  if drop is not None:
+    t0, t1 = (torch.as_tensor(x).reshape(-1, 1) for x in drop)  # [S or 1, 1]
+    masked = masked | ((kpos >= t0) & (kpos < t1))
+  s = (scale * scale_mul) * torch.einsum("bshd,bhtd->bhst", qd, kk)
+  if softcap and not no_softcap:
+    s = softcap * torch.tanh(s / softcap)
+  sabs = (scale * torch.einsum("bshd,bhtd->bhst", qd.abs(), kk.abs())).masked_fill(masked, 0.0).amax(-1)
+  w = s.masked_fill(masked, float("-inf")).softmax(-1).nan_to_num(0.0)
+  ref = torch.einsum("bhst,bhtd->bshd", w, vv)
+  absw = torch.einsum("bhst,bhtd->bshd", w, vv.abs())
+  eps_rel = 2 * (2.0 ** -24 * (hd + 8) * sabs + 2.0 ** -22 + 2.0 ** -22 * softcap) + 2.0 ** -24 * (2 * T + 16 + extra_acc)
+  eps_rel = eps_rel.permute(0, 2, 1)[..., None]  # [B, S, H, 1]
+  bound = (2.0 ** -8 * absw + eps_rel * absw) * (1 + 2.0 ** -8) + 2.0 ** -8 * ref.abs()
+  return ref, bound
+
+
+def prefill_worst_ratio(out, q, k, v, start_pos, scale=None, softcap=0.0, window=0) -> float:
+  """Worst |out - ref| / bound of one causal bf16 prefill: q [B, S, H, hd] at
+  positions start_pos.., k / v [B, KVH, start_pos + S, hd] the bf16 rows the
+  packed cache holds."""
+  q, k, v = (x.detach().cpu() for x in (q, k, v))
+  B, S, H, hd = q.shape
+  end = (start_pos + 1 + torch.arange(S)).expand(B, S)
+  ref, bound = prefill_reference(q, k.double(), v.double(), end, scale or hd ** -0.5, softcap, window)
+  worst = ((out.detach().cpu().double() - ref).abs() / bound).max().item()
+  print(f"bf16 prefill vs fp64 oracle: B={B} S={S} H={H}/{k.shape[1]} hd={hd} start_pos={start_pos} "
+        f"softcap={softcap} window={window}: worst err/bound {worst:.3f}")
+  return worst
+
+
+# ---------------------------------------------------------------------------
+# Prefill cases: four families stacked along the batch axis into one launch.
+#   limits  the last PF_M dims of a head row carry a one-hot position code:
+#           k[t] has amplitude a at dim hd - PF_M + t % PF_M, and q of the row
+#           at position p has amplitude a at the codes of p, p + 1 and, under
+#           a window, p - window + 1 and p - window, scale * a^2 = G. The
+#           row's last visible position, the first forbidden one, the window's
+#           first position and the one before it then each hold a sizeable
+#           share of the softmax at every row, however long. The other dims
+#           are random: q std 0.5, K std 2.5, V std 0.5.
+#   tiles   scores of std about 1, and V of half-tile t // 16 carries A_TILE in
+#           its own block of dims: a dropped or doubled half-tile moves every
+#           row that sees it.
+#   scores  every position is a marker: K lies along one anchor direction with
+#           factor 1 at even and 1 - GAP / gs at odd positions, q along the
+#           same anchor, so that even positions score gs (12, or 24 under a
+#           softcap, where the cap halves the gap) and odd ones gs - GAP; V
+#           carries A_SCORE in block 0 at even and in block 1 at odd positions,
+#           so the two blocks read back the weight of either parity.
+#   plain   random, q std 0.5, K std 2.5, V std 0.5.
+# Every family's cache holds +-1e30 bf16 poison from T = start_pos + S to the
+# capacity, and extra cache batches past the launch's are all poison.
+# ---------------------------------------------------------------------------
+
+PF_M = 64
+PF_FAMILIES = ("limits", "tiles", "scores", "plain")
+
+
+@dataclass(frozen=True)
+class PrefillSpec:
+  hd: int
+  B: int                 # sequences per family: the launch has 4 B
+  H: int
+  KVH: int
+  S: int
+  start: int
+  softcap: float = 0.0
+  window: int = 0
+  cap: int = 0
+  extra_batch: int = 0   # cache batches beyond the launch's
+  G: float = 5.0
+
+  @property
+  def name(self):
+    flags = f"-softcap{self.softcap:g}-window{self.window}" if self.softcap or self.window else ""
+    return f"hd{self.hd}-B{self.B}-H{self.H}x{self.KVH}-S{self.S}-at{self.start}{flags}"
+
+  @property
+  def scale(self):
+    return self.hd ** -0.5
+
+  @property
+  def T(self):
+    return self.start + self.S
+
+  @property
+  def qrows(self):       # q rows per workgroup: 4 waves x ATTN_PREFILL_NT x 16
+    return 128 if self.hd == 128 else 64
+
+  def tp0(self, s):
+    """first kv tile the q block of row s visits"""
+    return max(0, (self.start + s // self.qrows * self.qrows - self.window + 1) >> 5) if self.window else 0
+
+
+@dataclass
+class PrefillCase:
+  spec: PrefillSpec
+  fam: list              # family of each launch batch row
+  q: torch.Tensor        # [4 B, S, H, hd] bf16
+  kc: torch.Tensor       # [4 B + extra, KVH, cap, hd] bf16, poison from T on
+  vc: torch.Tensor
+  end: torch.Tensor      # [4 B, S] exclusive causal limit of each row
+  k: torch.Tensor        # [4 B, KVH, T, hd] fp64: the live rows
+  v: torch.Tensor
+  ref: torch.Tensor      # [4 B, S, H, hd] fp64
+  bound: torch.Tensor
+
+  def rows(self, fam):
+    return torch.tensor([f == fam for f in self.fam])
+
+  def reference(self, fam, **mutation):
+    """The reference of one family's sequences, mutated -> [B, S, H, hd]."""
+    sp, b = self.spec, self.rows(fam)
+    return prefill_reference(self.q[b], self.k[b], self.v[b], self.end[b], sp.scale, sp.softcap, sp.window, **mutation)[0]
+
+
+def _prefill_rows(sp, fam, g):
+  """One sequence of family `fam`: q [S, H, hd], k / v [KVH, T, hd], fp32."""
+  S, H, G, T, hd = sp.S, sp.H, sp.KVH, sp.T, sp.hd
+  rn = lambda *s: torch.randn(*s, generator=g)
+  pos, p = torch.arange(T), sp.start + torch.arange(S)
+  v = 0.5 * rn(G, T, hd)
+  if fam == "limits":
+    a = math.sqrt(sp.G / sp.scale)
+    q, k = 0.5 * rn(S, H, hd), 2.5 * rn(G, T, hd)
+    q[..., hd - PF_M:] = 0
+    k[..., hd - PF_M:] = 0
+    k[:, pos, hd - PF_M + pos % PF_M] = a
+    for off in (0, 1) + ((1 - sp.window, -sp.window) if sp.window else ()):
+      q[torch.arange(S), :, hd - PF_M + (p + off) % PF_M] = a
+  elif fam == "tiles":
+    q, k = rn(S, H, hd), rn(G, T, hd)
+    nblk = (T + 15) // 16
+    stride = hd // nblk
+    v[:, pos[:, None], (pos // 16)[:, None] * stride + torch.arange(min(stride, 8))] += A_TILE
+  elif fam == "scores":
+    u = torch.where(rn(hd) < 0, -1.0, 1.0)
+    gs = 24.0 if sp.softcap else 12.0
+    a = math.sqrt(gs / (sp.scale * hd))
+    q, k = 0.5 * rn(S, H, hd), 0.5 * rn(G, T, hd)
+    q -= (q @ u / hd)[..., None] * u   # the random parts are orthogonal to the anchor
+    k -= (k @ u / hd)[..., None] * u
+    q += a * u
+    k += torch.where(pos % 2 == 0, 1.0, 1.0 - GAP / gs)[:, None] * a * u
+    v[:, 0::2, 0:BW] += A_SCORE
+    v[:, 1::2, BW:2 * BW] += A_SCORE
+  else:
+    q, k = 0.5 * rn(S, H, hd), 2.5 * rn(G, T, hd)
+  return q, k, v
+
+
+_PREFILL_CASES = {}
+
+
+def prefill_case(sp: PrefillSpec) -> PrefillCase:
+  """The case of a spec with its unmutated reference, built once per process and shared."""
+  if sp in _PREFILL_CASES:
+    return _PREFILL_CASES[sp]
+  g = torch.Generator().manual_seed(2000 + 1000 * sp.S + sp.start + sp.hd)
+  fam, qs, ks, vs = [], [], [], []
+  for f in PF_FAMILIES:
+    for _ in range(sp.B):
+      q, k, v = _prefill_rows(sp, f, g)
+      fam.append(f); qs.append(q); ks.append(k); vs.append(v)
+  q, kb, vb = (torch.stack(x).bfloat16() for x in (qs, ks, vs))
+  Bl, T = len(fam), sp.T
+  sign = lambda: torch.where(torch.rand(Bl + sp.extra_batch, sp.KVH, sp.cap, sp.hd, generator=g) < 0.5, -1e30, 1e30).bfloat16()
+  kc, vc = sign(), sign()
+  kc[:Bl, :, :T], vc[:Bl, :, :T] = kb, vb
+  end = (sp.start + 1 + torch.arange(sp.S)).expand(Bl, sp.S).contiguous()
+  k, v = kb.double(), vb.double()
+  ref, bound = prefill_reference(q, k, v, end, sp.scale, sp.softcap, sp.window)
+  _PREFILL_CASES[sp] = PrefillCase(sp, fam, q, kc, vc, end, k, v, ref, bound)
+  return _PREFILL_CASES[sp]
+
+
+def prefill_mutations(c: PrefillCase):
+  """(name, family, reference kwargs, [S] mask of the rows it must move) for
+  every mutation that applies to the case. A row at position p sees [lo, end),
+  end = p + 1."""
+  sp = c.spec
+  S, T, w = sp.S, sp.T, sp.window
+  end = c.end[0]
+  lo = (end - w).clamp_min(0) if w else torch.zeros_like(end)
+  everyone, two = torch.ones(S, dtype=torch.bool), end - lo >= 2
+  muts = [("limit-1", "limits", dict(end_shift=-1), everyone),
+          ("limit+1", "limits", dict(end_shift=1), end < T)]   # the last row's next slot is poison, not a mutation
+  if w:
+    muts += [("window start+1", "limits", dict(lo_shift=1), end - w >= 0),
+             ("window start-1", "limits", dict(lo_shift=-1), end - w >= 1)]
+  # every half-tile, for the rows that see all 16 of its positions
+  for j in range(T // 16):
+    muts.append((f"half-tile {j}", "tiles", dict(drop=(16 * j, 16 * j + 16)), (lo <= 16 * j) & (end >= 16 * j + 16)))
+  # the first tile of each q block, dropped for the block's rows (a tile skip one tile late): the tiles
+  # rows that see one of its half-tiles whole, the limits rows whose first or last position lies in it
+  t0 = torch.tensor([32 * sp.tp0(s) for s in range(S)])
+  whole = ((lo <= t0) & (end >= t0 + 16)) | ((lo <= t0 + 16) & (end >= t0 + 32))
+  inside = lambda x: (x >= t0) & (x < t0 + 32)
+  muts += [("first tile", "tiles", dict(drop=(t0, t0 + 32)), whole),
+           ("first tile", "limits", dict(drop=(t0, t0 + 32)), inside(end - 1) | inside(lo))]
+  muts.append(("scale*sqrt2", "scores", dict(scale_mul=math.sqrt(2.0)), two))
+  if sp.softcap:
+    muts.append(("no softcap", "scores", dict(no_softcap=True), two))
+  if sp.KVH > 1:
+    rep = sp.H // sp.KVH
+    for f in PF_FAMILIES:
+      muts.append(("neighbouring kv head", f, dict(kv_map=[(h // rep + 1) % sp.KVH for h in range(sp.H)]), everyone))
+  return muts
+
+
+def prefill_emulate(c: PrefillCase) -> torch.Tensor:
+  """The kernel's loop in torch fp32 on the CPU, over the cache as the kernel
+  reads it (poison included): one q block of spec.qrows rows at a time, kv
+  tiles of 32 positions from tp0 to the block's causal end, online softmax with
+  the kernel's alpha and its -inf guard, P rounded once to bf16 for the PV
+  product while the denominator keeps the fp32 p, fp32 accumulation, the final
+  multiply by 1 / l and the bf16 rounding -> [4 B, S, H, hd] fp32."""
+  sp = c.spec
+  Bl, S, H, hd = c.q.shape
+  rep = H // sp.KVH
+  q = c.q.float().permute(0, 2, 1, 3)                          # [Bl, H, S, hd]
+  kk = c.kc[:Bl].float().repeat_interleave(rep, dim=1)         # [Bl, H, cap, hd]
+  vv = c.vc[:Bl].float().repeat_interleave(rep, dim=1)
+  scale, softcap = torch.tensor(sp.scale, dtype=torch.float32), torch.tensor(sp.softcap, dtype=torch.float32)
+  out = torch.zeros(Bl, H, S, hd)
+  ninf = torch.tensor(-math.inf)
+  for r0 in range(0, S, sp.qrows):
+    r1 = min(r0 + sp.qrows, S)
+    kv_end = sp.start + r1
+    rowpos = sp.start + torch.arange(r0, r1)[:, None]
+    m = torch.full((Bl, H, r1 - r0), -math.inf)
+    l = torch.zeros(Bl, H, r1 - r0)
+    acc = torch.zeros(Bl, H, r1 - r0, hd)
+    for tp in range(sp.tp0(r0), (kv_end + 31) >> 5):
+      pos = torch.arange(32 * tp, 32 * tp + 32)
+      s = (q[:, :, r0:r1] @ kk[:, :, pos].transpose(-1, -2)) * scale
+      if sp.softcap:
+        s = softcap * torch.tanh(s * (1.0 / softcap))
+      ok = (pos <= rowpos) & (pos < kv_end)
+      if sp.window:
+        ok = ok & (pos > rowpos - sp.window)
+      s = torch.where(ok, s, ninf)
+      mn = torch.maximum(m, s.amax(-1))
+      dead = mn == -math.inf                                   # nothing visible so far: the kernel's guard
+      mz = torch.where(dead, torch.zeros_like(mn), mn)
+      alpha = torch.where(dead, torch.ones_like(l), torch.where(l > 0, torch.exp(m - mz), torch.zeros_like(l)))
+      p = torch.where(dead[..., None], torch.zeros_like(s), torch.exp(s - mz[..., None]))
+      l = l * alpha + p.sum(-1)
+      acc = acc * alpha[..., None] + p.bfloat16().float() @ vv[:, :, pos]
+      m = mn
+    inv = torch.where(l > 0, 1.0 / l, torch.zeros_like(l))
+    out[:, :, r0:r1] = acc * inv[..., None]
+  return out.bfloat16().float().permute(0, 2, 1, 3)
+
+
+# The cases of tests/test_attn_prefill_oracle_gpu.py, the smallest shapes at
+# which each mechanism of the kernel exists; tests/test_attn_prefill_oracle_cpu.py
+# checks every one of them for mutation margins and the emulator.
+PREFILL_SPECS = [
+  PrefillSpec(128, 1, 1, 1, 16, 0, cap=64),                               # one sub-tile, one tile
+  PrefillSpec(128, 2, 4, 2, 130, 0, cap=192, extra_batch=1),              # second q block with 2 live rows and clamped q rows; cache batch > launch batch
+  PrefillSpec(128, 2, 2, 1, 48, 40, cap=128),                             # offset that is no multiple of 32
+  PrefillSpec(128, 1, 2, 2, 33, 95, cap=128),                             # start_pos + S == T32: full last tile, no spare tile
+  PrefillSpec(128, 1, 4, 2, 100, 30, softcap=30.0, window=40, cap=160),   # window < q block: late rows meet wholly masked tiles while m = -inf
+  PrefillSpec(128, 1, 2, 1, 140, 200, window=48, cap=384),                # tp0 > 0, different for the two q blocks
+  PrefillSpec(256, 2, 4, 2, 70, 0, cap=128),                              # 64-row q blocks, NT = 1
+  PrefillSpec(256, 1, 8, 1, 70, 27, cap=128),                             # 8 q heads per kv head
+  PrefillSpec(256, 1, 2, 1, 40, 50, softcap=30.0, window=40, cap=128),    # gemma2 flags
+]

@@ -15,7 +15,7 @@ several tiles per wave 0.38/0.47."""
 import pytest
 import torch
 
-from attn_oracle import pack_k, pack_v
+from attn_oracle import pack_k, pack_v, prefill_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -23,26 +23,8 @@ pytestmark = pytest.mark.gpu
 def _reference(q, k, v, q_start, scale, softcap, window, nsplit, shift=0):
   """fp64 over q's bf16 values and the k / v [B, KVH, T, hd] the kernel reads; row s of sequence b
   sees [end - window, end) with end = q_start[b] + s + 1 + shift -> (ref, bound), [B, S, H, hd]."""
-  B, S, H, hd = q.shape
-  T, rep = k.shape[2], H // k.shape[1]
-  qd = q.double()
-  kk, vv = k.repeat_interleave(rep, dim=1), v.repeat_interleave(rep, dim=1)
-  end = (torch.tensor(q_start)[:, None] + torch.arange(S)[None, :] + 1 + shift)[:, None, :, None]  # [B, 1, S, 1]
-  kpos = torch.arange(T)
-  masked = kpos >= end
-  if window:
-    masked = masked | (kpos < end - window)
-  s = scale * torch.einsum("bshd,bhtd->bhst", qd, kk)
-  if softcap:
-    s = softcap * torch.tanh(s / softcap)
-  sabs = (scale * torch.einsum("bshd,bhtd->bhst", qd.abs(), kk.abs())).masked_fill(masked, 0.0).amax(-1)
-  w = s.masked_fill(masked, float("-inf")).softmax(-1).nan_to_num(0.0)  # a row that sees nothing gives 0
-  ref = torch.einsum("bhst,bhtd->bshd", w, vv)
-  absw = torch.einsum("bhst,bhtd->bshd", w, vv.abs())
-  eps_rel = 2 * (2.0 ** -24 * (hd + 8) * sabs + 2.0 ** -22 + 2.0 ** -22 * softcap) + 2.0 ** -24 * (2 * T + 16 + nsplit + 2)
-  eps_rel = eps_rel.permute(0, 2, 1)[..., None]  # [B, S, H, 1]
-  bound = (2.0 ** -8 * absw + eps_rel * absw) * (1 + 2.0 ** -8) + 2.0 ** -8 * ref.abs()
-  return ref, bound
+  end = torch.tensor(q_start)[:, None] + torch.arange(q.shape[1])[None, :] + 1 + shift  # [B, S]
+  return prefill_reference(q, k, v, end, scale, softcap, window, extra_acc=nsplit + 2)
 
 
 @pytest.mark.parametrize("fp8", [False, True], ids=["bf16", "fp8"])

@@ -346,6 +346,7 @@ def test_prefill(hip, B, H, KVH, S, start):
   ref = torch_ref.attn_prefill(q, k, v, start, S)
   ok, err = _close(out, ref, 3e-2)
   assert ok, err
+  assert ao.prefill_worst_ratio(out, q, k, v, start) <= 1.0
 
 
 def test_prefill_strided_q(hip):
@@ -359,6 +360,7 @@ def test_prefill_strided_q(hip):
   ref = torch_ref.attn_prefill(q.contiguous(), k, v, 0, S)
   ok, err = _close(out, ref, 3e-2)
   assert ok, err
+  assert ao.prefill_worst_ratio(out, q, k, v, 0) <= 1.0
 
 
 @pytest.mark.parametrize("softcap,window,start", [(50.0, 0, 0), (0.0, 48, 0), (30.0, 48, 32)])
@@ -371,6 +373,7 @@ def test_prefill_softcap_window(hip, softcap, window, start):
   ref = torch_ref.attn_prefill(q, k, v, start, S, scale, softcap, window)
   ok, err = _close(out, ref, 3e-2)
   assert ok, err
+  assert ao.prefill_worst_ratio(out, q, k, v, start, scale, softcap, window) <= 1.0
 
 
 def test_prefill_window_tile_skip(hip):
@@ -385,6 +388,7 @@ def test_prefill_window_tile_skip(hip):
   ref = torch_ref.attn_prefill(q, k, v, start, S, scale, 0.0, window)
   ok, err = _close(out, ref, 3e-2)
   assert ok, err
+  assert ao.prefill_worst_ratio(out, q, k, v, start, scale, 0.0, window) <= 1.0
 
 
 # ---------------- 7. cache ----------------

@@ -5,32 +5,16 @@ packed-only fp8 cache against today's plain-cache route."""
 import pytest
 import torch
 
-from attn_oracle import pack_k, pack_v
+from attn_oracle import pack_k, pack_v, prefill_reference
 
 pytestmark = pytest.mark.gpu
 
 
 def _reference(q, k, v, start_pos, scale, softcap, window):
   """fp64 over q's bf16 values and the dequantised k / v [B, KVH, T, hd] -> (ref, bound), [B, S, H, hd]."""
-  B, S, H, hd = q.shape
-  T, rep = start_pos + S, H // k.shape[1]
-  qd = q.double()
-  kk, vv = k.repeat_interleave(rep, dim=1), v.repeat_interleave(rep, dim=1)
-  qpos, kpos = start_pos + torch.arange(S)[:, None], torch.arange(T)[None, :]
-  masked = kpos > qpos
-  if window:
-    masked = masked | (kpos <= qpos - window)
-  s = scale * torch.einsum("bshd,bhtd->bhst", qd, kk)
-  if softcap:
-    s = softcap * torch.tanh(s / softcap)
-  sabs = (scale * torch.einsum("bshd,bhtd->bhst", qd.abs(), kk.abs())).masked_fill(masked, 0.0).amax(-1)
-  w = s.masked_fill(masked, float("-inf")).softmax(-1)
-  ref = torch.einsum("bhst,bhtd->bshd", w, vv)
-  absw = torch.einsum("bhst,bhtd->bshd", w, vv.abs())
-  eps_rel = 2 * (2.0 ** -24 * (hd + 8) * sabs + 2.0 ** -22 + 2.0 ** -22 * softcap) + 2.0 ** -24 * (2 * T + 16)
-  eps_rel = eps_rel.permute(0, 2, 1)[..., None]  # [B, S, H, 1]
-  bound = (2.0 ** -8 * absw + eps_rel * absw) * (1 + 2.0 ** -8) + 2.0 ** -8 * ref.abs()
-  return ref, bound
+  B, S = q.shape[:2]
+  end = (start_pos + 1 + torch.arange(S)).expand(B, S)
+  return prefill_reference(q, k, v, end, scale, softcap, window)
 
 
 @pytest.mark.parametrize("hd,B,H,KVH,S,start_pos,softcap,window", [

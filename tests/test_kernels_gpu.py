@@ -431,6 +431,7 @@ def test_attn_prefill_mfma(hip, B, H, KVH, S, start):
   out = _hip_ops.attn_prefill_mfma(q, kp, vp, start).float()
   ref = torch_ref.attn_prefill(q, k, v, start, S).float()
   assert torch.allclose(out, ref, atol=3e-2, rtol=3e-2), (out - ref).abs().max()
+  assert ao.prefill_worst_ratio(out, q, k, v, start) <= 1.0
 
 
 def test_attn_prefill_mfma_strided_q(hip):
@@ -446,6 +447,7 @@ def test_attn_prefill_mfma_strided_q(hip):
   out = _hip_ops.attn_prefill_mfma(q, kp, vp, 0).float()
   ref = torch_ref.attn_prefill(q.contiguous(), k, v, 0, S).float()
   assert torch.allclose(out, ref, atol=3e-2, rtol=3e-2), (out - ref).abs().max()
+  assert ao.prefill_worst_ratio(out, q, k, v, 0) <= 1.0
 
 
 def test_moe_fp8_matches_bf16(hip, monkeypatch):
@@ -554,6 +556,7 @@ def test_attn_prefill_mfma_softcap_window(hip, softcap, window, start):
   out = _hip_ops.attn_prefill_mfma(q, kp, vp, start, scale, softcap, window).float()
   ref = torch_ref.attn_prefill(q, k, v, start, S, scale, softcap, window).float()
   assert torch.allclose(out, ref, atol=3e-2, rtol=3e-2), (out - ref).abs().max()
+  assert ao.prefill_worst_ratio(out, q, k, v, start, scale, softcap, window) <= 1.0
 
 
 def test_rmsnorm_gemma_bias(hip):
@@ -1348,3 +1351,4 @@ def test_attn_prefill_mfma_window_tile_skip(hip):
   out = _hip_ops.attn_prefill_mfma(q, kp, vp, start, scale, 0.0, window).float()
   ref = torch_ref.attn_prefill(q, k, v, start, S, scale, 0.0, window).float()
   assert torch.allclose(out, ref, atol=3e-2, rtol=3e-2), (out - ref).abs().max()
+  assert ao.prefill_worst_ratio(out, q, k, v, start, scale, 0.0, window) <= 1.0
