@@ -31,7 +31,7 @@ from xotorch_amd import ops
 from xotorch_amd.models.base import ShardBase, ragged_decode_rows
 from xotorch_amd.models.config import ModelConfig
 from xotorch_amd.models.llama import XotLinear
-from xotorch_amd.models.moe import expert_loop, moe_decode, sorted_expert_prefill
+from xotorch_amd.models.moe import expert_loop, moe_decode, moe_prefill, moe_prefill_fits, sorted_expert_prefill
 from xotorch_amd.ops.torch_ref import rmsnorm as rmsnorm_ref
 from xotorch_amd.shard import Shard
 
@@ -323,13 +323,16 @@ class DsMoE(nn.Module):
     self.wp_down = torch.stack(dn).contiguous()
 
   def _forward_decode(self, flat):
-    """Fused router, then the static-capacity pipeline (moe.moe_decode)."""
+    """Fused router, then the static-capacity pipeline (moe.moe_decode) or,
+    above 256 tokens under XOT_MOE_PREFILL=1, the ragged one (moe.moe_prefill)."""
     cfg = self.cfg
     logits = nn.functional.linear(flat.float(), self.gate_weight.float())
     idx, w = ops.moe_route(logits.contiguous(), self.e_score_correction_bias.float().contiguous(),
                            cfg.n_experts_per_tok, 1, max(1, cfg.n_group),
                            max(1, cfg.topk_group), cfg.routed_scaling_factor,
                            bool(cfg.norm_topk_prob))
+    if flat.shape[0] > 256:
+      return moe_prefill(flat, idx, w, cfg.n_experts, cfg.moe_intermediate_dim, self.wp_gate_up, self.wp_down)
     return moe_decode(flat, idx, w, cfg.n_experts, cfg.moe_intermediate_dim, self.experts,
                       self.wp_gate_up, self.wp_down)
 
@@ -338,7 +341,7 @@ class DsMoE(nn.Module):
     flat = x.view(-1, D)
     T = flat.shape[0]
     if (self.wp_gate_up is not None and x.is_cuda and not torch.is_grad_enabled()
-        and 1 <= T <= 256):
+        and (1 <= T <= 256 or moe_prefill_fits(flat, self.wp_gate_up))):
       out = self._forward_decode(flat) + self.shared_experts(flat)
       return out.to(x.dtype).view(B, S, D)
     if torch.cuda.is_available() and x.is_cuda and torch.cuda.is_current_stream_capturing():

@@ -26,7 +26,7 @@ from xotorch_amd.engine.kvcache import LayerKV
 from xotorch_amd.models.base import ShardBase
 from xotorch_amd.models.config import ModelConfig
 from xotorch_amd.models.linear import XotLinear, auto_pick, decode_rows
-from xotorch_amd.models.moe import expert_loop, moe_decode, sorted_expert_prefill
+from xotorch_amd.models.moe import expert_loop, moe_decode, moe_prefill, moe_prefill_fits, sorted_expert_prefill
 from xotorch_amd.shard import Shard
 
 
@@ -204,6 +204,8 @@ class MoEMLP(nn.Module):
       return
     if self.wp_gate_up is None and all(e.gate_up_proj.weight_packed is not None for e in self.experts) \
        and all(e.down_proj.weight_packed is not None for e in self.experts):
+      # moe_decode and moe_prefill read the plain [gate; up] pack (glu_store_module flags no expert)
+      assert not any(e.gate_up_proj.glu_packed for e in self.experts)
       self.wp_gate_up = torch.stack([e.gate_up_proj.weight_packed for e in self.experts]).contiguous()
       self.wp_down = torch.stack([e.down_proj.weight_packed for e in self.experts]).contiguous()
       for e in self.experts:  # the grouped stack supersedes the per-expert packs
@@ -223,6 +225,11 @@ class MoEMLP(nn.Module):
     T = flat.shape[0]
     if x.is_cuda and not torch.is_grad_enabled() and T <= 256:
       return self._forward_decode(flat).view(B, S, D).to(x.dtype)
+    if moe_prefill_fits(flat, self.wp_gate_up):
+      # XOT_MOE_PREFILL=1: fused router, then the ragged grouped GEMMs (no host sync)
+      selected, weights = ops.moe_route(self.gate(flat).float().contiguous(), None, self.top_k, 0)
+      return moe_prefill(flat, selected, weights, self.n_experts, self.intermediate,
+                         self.wp_gate_up, self.wp_down).view(B, S, D)
     # NOTE: chunking the static grouped path over 256-token slices for
     # prefill was measured 1.5-2.5x WORSE TTFT (every chunk re-streams the
     # full expert weights; the eager loop streams each expert once with a

@@ -1,5 +1,6 @@
 """What the routed MoE blocks (llama.MoEMLP, deepseek_v3.DsMoE) share after
-routing: the static-capacity decode pipeline and the sorted prefill."""
+routing: the static-capacity decode pipeline, the ragged static-shape prefill
+(XOT_MOE_PREFILL=1) and the sorted prefill."""
 from __future__ import annotations
 
 import torch
@@ -63,6 +64,27 @@ def moe_decode(flat, selected, weights, E: int, I: int, experts, wp_gate_up=None
   out = torch.zeros(T, D, dtype=torch.float32, device=dev)
   out.index_add_(0, gather_tok, y.float() * scale.reshape(-1, 1))
   return out
+
+
+def moe_prefill_fits(flat, wp_gate_up) -> bool:
+  """Whether MoEMLP / DsMoE send this forward to moe_prefill: more than 256
+  tokens (moe_decode has the rest), bf16 activations and stacks, inference,
+  and the XOT_MOE_PREFILL knob."""
+  return (flat.shape[0] > 256 and wp_gate_up is not None and flat.is_cuda and flat.dtype == torch.bfloat16
+          and not torch.is_grad_enabled() and ops.moe_prefill_enabled())
+
+
+def moe_prefill(flat, selected, weights, E: int, I: int, wp_gate_up, wp_down):
+  """Static-shape routed experts for any T on the bf16 stacked packs: a dense
+  device-side plan (no capacity padding, no host read), ONE ragged grouped
+  launch per projection (gate_up gathers its rows from flat and applies SwiGLU
+  in its store; neither flat[tok_sorted] nor the [A, 2I] product exists), then
+  the deterministic combine. Same launches whatever the routing: capturable.
+  flat [T, D] bf16, ids / weights [T, k] -> [T, D] bf16."""
+  sorted_tok, inv_pos, *tiles = ops.moe_plan(selected.to(torch.int32).contiguous(), E, ops.moe_ragged_bm())
+  h = ops.moe_gemm_ragged(flat.contiguous(), wp_gate_up, 2 * I, sorted_tok, *tiles, True, True)
+  y = ops.moe_gemm_ragged(h, wp_down, flat.shape[1], sorted_tok, *tiles, False, False)
+  return ops.moe_combine(y, inv_pos, weights.float().contiguous())
 
 
 def sorted_expert_prefill(flat, weights, selected, experts):

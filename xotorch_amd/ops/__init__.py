@@ -303,6 +303,12 @@ skinny_gemm_mxfp4 = _binding("skinny_gemm_mxfp4")
 moe_route = _binding("moe_route")
 moe_build = _binding("moe_build")      # (ids int32 [T, k], E, C): counting sort -> (gather_tok [E*C], inv_pos [T, k])
 moe_combine = _binding("moe_combine")  # (y [E*C, D], inv_pos, weights fp32) -> [T, D] bf16, deterministic
+# (ids int32 [T, k], E, BM = moe_ragged_bm()): dense counting sort -> (sorted_tok [A], inv_pos [T, k], tile_expert [NB],
+# tile_row0 [NB], offsets [E + 1]), A = T * k, NB = ceil(A / BM) + E, dead tiles carry expert -1; no host sync
+moe_plan = _binding("moe_plan")
+# (x, stacked wp, N, sorted_tok, tile_expert, tile_row0, offsets, gather, glu): gate_up (both true; x = flat [T, D],
+# N = 2I -> silu(gate) * up [A, I]) or down (both false; x [A, I] -> [A, N]) of every expert in one ragged launch
+moe_gemm_ragged = _binding("moe_gemm_ragged")
 # MLA (models/deepseek_v3.py) on the latent cache's packed copies (kp, vp; e4m3 with k_scale in fp8-KV mode)
 # (ckv, latent norm w, cos, sin, int32 positions, lat_c, rot_c, kp, vp, eps, interleave, k_scale | None): norm + rope + append
 mla_prep_append = _binding("mla_prep_append")
@@ -313,6 +319,19 @@ attn_decode_mla = _binding("attn_decode_mla")  # (q, kp, vp, seq_lens, scale, q_
 # causal flash prefill, nope 128 / rope 64 / v 128: (q [B,S,H,192], kvx [B,T,H,256] = the kv_b_proj output read in
 # place, rot [B,1,Tcap,64] = the plain rope-key cache, start_pos, scale) -> [B, S, H, 128], T = start_pos + S
 attn_prefill_mla = _binding("attn_prefill_mla")
+
+
+def moe_ragged_bm() -> int:
+  """Slots per tile the ragged grouped GEMM was built for (moe_plan's BM)."""
+  return _gpu().MOE_RAGGED_BM
+
+
+def moe_prefill_enabled() -> bool:
+  """XOT_MOE_PREFILL (default 0, read per call): routed experts of a forward
+  with more than 256 tokens run on moe_plan + moe_gemm_ragged (models/moe.py
+  moe_prefill: static shape, no host sync, graph-capturable) where the bf16
+  stacks exist; 0 keeps the sorted per-expert library GEMMs."""
+  return os.getenv("XOT_MOE_PREFILL", "0") == "1"
 
 
 def mla_prefill_enabled() -> bool:

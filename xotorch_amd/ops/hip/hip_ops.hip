@@ -1314,6 +1314,123 @@ __global__ __launch_bounds__(256) void moe_build_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// MoE prefill plan: the DENSE counterpart of moe_build_kernel. No capacity
+// padding: the A = T*k assignments are counting-sorted by expert into dense
+// slots [0, A), and a tile table tells the ragged grouped GEMM
+// (moe_gemm_ragged_kernel) which expert and which BM slots each workgroup
+// owns. Static shape throughout: NB = ceil(A / BM) + E table entries bound
+// sum_e ceil(m_e / BM) for any routing, tiles past the live count say expert
+// -1, and nothing is read back by the host.
+//
+// A reaches a few hundred thousand (T = 32768, k = 8), where moe_build's one
+// workgroup would walk the list alone, so the list is cut into G <= 256
+// contiguous chunks of >= 512 assignments, one workgroup each, in two
+// launches and without global atomics (nothing to zero between calls, so the
+// pair is graph-capturable):
+//   moe_plan_count_kernel  chunk g -> counts[g][e] (LDS histogram, every
+//                          entry written)
+//   moe_plan_kernel        every workgroup sums the G x E table (<= 256 loads
+//                          per thread) into the experts' totals and its own
+//                          first slot per expert (offsets[e] + the chunks
+//                          before it), then scatters its chunk with LDS
+//                          cursors; workgroup 0 also writes offsets and the
+//                          tile table.
+// Row order inside an expert: chunks land in chunk order, the rows of one
+// chunk in whatever order its LDS atomics resolve, so it is NOT deterministic.
+// It need not be: a row's GEMM result does not depend on its slot, and
+// moe_combine sums a token's k rows in k order through inv_pos, so the
+// block's output is deterministic anyway.
+// Ids outside [0, E) (moe_route never writes one) are skipped, not counted:
+// their inv_pos is slot 0 and no tile covers the slots left over at the end.
+// ---------------------------------------------------------------------------
+constexpr int MOE_PLAN_CHUNK = 512;  // fewest assignments a workgroup takes
+constexpr int MOE_PLAN_MAXG = 256;   // most workgroups (the G loop per thread)
+
+__global__ __launch_bounds__(256) void moe_plan_count_kernel(
+    const int* __restrict__ idx, int* __restrict__ block_counts, int A, int E) {
+  __shared__ int counts[256];
+  const int tid = threadIdx.x;
+  const int per = (A + gridDim.x - 1) / gridDim.x;
+  const int a0 = blockIdx.x * per, a1 = min(a0 + per, A);
+  counts[tid] = 0;
+  __syncthreads();
+  for (int a = a0 + tid; a < a1; a += 256) {
+    const unsigned e = (unsigned)idx[a];
+    if (e < (unsigned)E) atomicAdd(&counts[e], 1);
+  }
+  __syncthreads();
+  if (tid < E) block_counts[blockIdx.x * E + tid] = counts[tid];
+}
+
+__global__ __launch_bounds__(256) void moe_plan_kernel(
+    const int* __restrict__ idx, const int* __restrict__ block_counts,
+    int* __restrict__ sorted_tok, int* __restrict__ inv_pos,
+    int* __restrict__ tile_expert, int* __restrict__ tile_row0, int* __restrict__ offsets,
+    int A, int k, int E, int BM, int NB) {
+  __shared__ int cnt[256];      // rows of expert e
+  __shared__ int cursor[256];   // rows of e in the chunks before this one, then the scatter cursor
+  __shared__ int off[257];      // exclusive prefix of cnt: first dense slot of e
+  __shared__ int tstart[257];   // exclusive prefix of ceil(cnt / BM): first tile of e
+  const int tid = threadIdx.x;
+  const int G = gridDim.x, b = blockIdx.x;
+  int tot = 0, before = 0;
+  if (tid < E)
+    for (int g = 0; g < G; ++g) {
+      const int c = block_counts[g * E + tid];
+      tot += c;
+      if (g < b) before += c;
+    }
+  cnt[tid] = tot;
+  cursor[tid] = before;
+  __syncthreads();
+  if (tid == 0) {  // E <= 256: serial prefix, as moe_build
+    int run = 0, trun = 0;
+    for (int e = 0; e < E; ++e) {
+      off[e] = run;
+      tstart[e] = trun;
+      run += cnt[e];
+      trun += (cnt[e] + BM - 1) / BM;
+    }
+    off[E] = run;
+    tstart[E] = trun;
+  }
+  __syncthreads();
+  if (b == 0) {
+    for (int e = tid; e <= E; e += 256) offsets[e] = off[e];
+    const int live = tstart[E];  // <= NB for any routing
+    for (int i = tid; i < NB; i += 256) {
+      int e = -1, r0 = 0;
+      if (i < live) {
+        // last e with tstart[e] <= i: an empty expert shares its tstart with
+        // the next one and is stepped over
+        int lo = 0, hi = E - 1;
+        while (lo < hi) {
+          const int mid = (lo + hi + 1) >> 1;
+          if (tstart[mid] <= i) lo = mid; else hi = mid - 1;
+        }
+        e = lo;
+        r0 = off[e] + (i - tstart[e]) * BM;
+      }
+      tile_expert[i] = e;
+      tile_row0[i] = r0;
+    }
+  }
+  if (tid < E) cursor[tid] += off[tid];
+  __syncthreads();
+  const int per = (A + G - 1) / G;
+  const int a0 = b * per, a1 = min(a0 + per, A);
+  for (int a = a0 + tid; a < a1; a += 256) {
+    const unsigned e = (unsigned)idx[a];
+    int slot = 0;
+    if (e < (unsigned)E) {
+      slot = atomicAdd(&cursor[e], 1);
+      sorted_tok[slot] = a / k;
+    }
+    inv_pos[a] = slot;
+  }
+}
+
 // out[t, :] = sum_j w[t, j] * y[inv_pos[t*k + j], :]   (fp32 accumulate)
 __global__ __launch_bounds__(256) void moe_combine_kernel(
     const unsigned short* __restrict__ y, const int* __restrict__ inv_pos,
@@ -3249,6 +3366,197 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Ragged grouped expert GEMM (MoE prefill, T > 256): one launch runs a
+// projection of EVERY expert over the dense sorted assignment list of
+// moe_plan_kernel. Workgroup (blockIdx.x = n tile, blockIdx.y = table entry)
+// computes Y[slot, n] = X[row(slot), :] . W[e][n, :] for the BM = MT * 32
+// slots [row0, min(row0 + BM, offsets[e + 1])) of its tile and the 128 weight
+// rows of its n tile. A table entry with expert -1 returns before any barrier.
+//
+// Operands as in skinny_gemm_packed_kernel, D^T = W . X^T on
+// v_mfma_f32_32x32x16_bf16: wave wv streams the A fragments of its own 32-row
+// weight tile straight from the stacked pack [E][N/32][K/16][64][8] (1 KB
+// coalesced wave loads, two K-steps in flight; plain cached loads, not
+// non-temporal: the other row tiles of the expert read the same bytes), the
+// BM x 64 X image of a K-step is staged through LDS (row stride 72), double-
+// buffered, one barrier per step, and every wave reads all of it as B.
+//   GATHER  (gate_up) slot r stages row sorted_tok[row0 + r] of flat [T, K];
+//           a row is contiguous, so a thread's 16 B piece and its 7
+//           neighbours still make one 128 B line. The gathered copy never
+//           exists.
+//   ragged  slots at or past the tile's end stage the tile's LAST live row
+//           (finite values, no read past [0, A) / [0, T)) and are never
+//           stored: the clamp-on-load idiom of the chunk attention kernels.
+//   N edge  the pack guarantees N % 32 == 0 only (I = 1408 = 44 x 32): a wave
+//           whose tile lies past N loads and stores nothing, but stages X and
+//           reaches every barrier.
+//   GLU     (gate_up, W = the plain [gate; up] stack, N = 2I) a wave runs TWO
+//           A streams, gate tile j and up tile j + I/32, against the same B
+//           fragments into the same D layout, so a lane holds gate and up of
+//           one (row, column). Both sums are rounded to bf16 as the plain
+//           store rounds them, then swiglu_bf16: the bits of swiglu_packed on
+//           the bf16 [A, 2I] output, which never exists. Y is H [A, I].
+// The store is skinny_store_acc's unsplit bf16 layout with a row mask.
+// Nothing is scattered or weighted here: moe_combine stays the one place
+// where a token's k rows are summed, in k order.
+//
+// Register budget (MT = 4, 256 threads): GLU holds 2 x 4 x 16 = 128
+// accumulators, 2 streams x 2 steps x 4 fragments = 64 VGPRs of A, 16 of
+// staged X and 8 of row pointers; the design target is <= 256 VGPR + AGPR,
+// two workgroups per CU (2 x 36 KB LDS), scratch 0. The down instantiation has
+// half the accumulators and half the A stream.
+// ---------------------------------------------------------------------------
+template <int MT, bool GATHER, bool GLU>
+__global__ __launch_bounds__(256, 2) void moe_gemm_ragged_kernel(
+    const unsigned short* __restrict__ Wp, const unsigned short* __restrict__ X,
+    unsigned short* __restrict__ Y, const int* __restrict__ sorted_tok,
+    const int* __restrict__ tile_expert, const int* __restrict__ tile_row0,
+    const int* __restrict__ offsets, int N, int K, int A, int T, int E) {
+  constexpr int BM = MT * 32;
+  constexpr int XROW = 64 + 8;       // padded LDS row stride (elems): conflict-free b128
+  constexpr int XIMG = BM * XROW;    // elems per image
+  constexpr int PPT = BM / 32;       // 16 B pieces per thread per step: row = tid/8 + 32 i
+  constexpr int NS = GLU ? 2 : 1;    // A streams per wave
+  const int e = tile_expert[blockIdx.y];
+  if (e < 0 || e >= E) return;
+  const int row0 = min(max(tile_row0[blockIdx.y], 0), A - 1);
+  const int rend = max(row0 + 1, min(min(row0 + BM, offsets[e + 1]), A));  // one past the last live slot
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = tid >> 6;
+
+  __shared__ unsigned short xs[2 * XIMG];
+
+  // A streams: NOUT = columns of Y; tile j of a GLU launch pairs gate tile j
+  // with up tile j + NOUT/32
+  const int NOUT = GLU ? N >> 1 : N;
+  const int j32 = blockIdx.x * 4 + wv;
+  const bool live = j32 * 32 < NOUT;  // wave-uniform
+  const size_t tile_elems = (size_t)(K >> 4) * 512;
+  const unsigned short* wp[NS];
+#pragma unroll
+  for (int g = 0; g < NS; ++g)
+    wp[g] = Wp + ((size_t)e * (N >> 5) + (live ? j32 + g * (NOUT >> 5) : 0)) * tile_elems + (size_t)lane * 8;
+
+  // X stage: piece i of thread tid is 16 B at column (tid % 8) * 8 of slot
+  // row0 + tid / 8 + 32 i, clamped to the last live slot
+  const unsigned short* xp[PPT];
+#pragma unroll
+  for (int i = 0; i < PPT; ++i) {
+    const int slot = min(row0 + (tid >> 3) + 32 * i, rend - 1);
+    const int src = GATHER ? min(max(sorted_tok[slot], 0), T - 1) : slot;
+    xp[i] = X + (size_t)src * K + (tid & 7) * 8;
+  }
+  const int xsb = (tid >> 3) * XROW + (tid & 7) * 8;
+
+  floatx16 acc[NS][MT];
+#pragma unroll
+  for (int g = 0; g < NS; ++g)
+#pragma unroll
+    for (int t = 0; t < MT; ++t) acc[g][t] = (floatx16)(0.f);
+
+  const int nsteps = K >> 6;
+  ushort8 xv[PPT];
+  bf16x8 a_buf[2][NS][4];
+
+#define MRG_XLOAD(STEP)                                                                        \
+  _Pragma("unroll")                                                                            \
+  for (int i = 0; i < PPT; ++i) xv[i] = *(const ushort8*)(xp[i] + (size_t)(STEP) * 64);
+#define MRG_XSTORE(IMG)                                                                        \
+  _Pragma("unroll")                                                                            \
+  for (int i = 0; i < PPT; ++i) *(ushort8*)(xs + (IMG) * XIMG + xsb + i * 32 * XROW) = xv[i];
+  // slot BUF <- the K-step that starts OFF fragments past wp[]
+#define MRG_ALOAD(BUF, OFF)                                                                    \
+  _Pragma("unroll")                                                                            \
+  for (int g = 0; g < NS; ++g) {                                                               \
+    _Pragma("unroll")                                                                          \
+    for (int u = 0; u < 4; ++u)                                                                \
+      a_buf[BUF][g][u] = load_bf16x8(wp[g] + ((OFF) + u) * 512);                               \
+  }
+
+  MRG_XLOAD(0)
+  if (live) {
+    MRG_ALOAD(0, 0)
+    MRG_ALOAD(1, (nsteps > 1 ? 4 : 0))  // clamp: no read past the tile at nsteps == 1
+#pragma unroll
+    for (int g = 0; g < NS; ++g) wp[g] += 8 * 512;
+  }
+  MRG_XSTORE(0)
+  __syncthreads();
+
+  // Step s reads LDS image BUF (= s & 1) and fills the other one for step
+  // s + 1: the barrier that ended step s - 1 is what lets every wave overwrite
+  // the image step s - 1 read. BUF is a compile-time constant (a dynamic A
+  // buffer index spills the array, see skinny_gemm_packed_kernel), and the last
+  // step carries the same MFMA-write -> accumulator-read nops on its edge to the
+  // store as that kernel (SGP_STEP_TAIL), for the reason given there.
+#define MRG_STEP(BUF)                                                                          \
+  {                                                                                            \
+    const bool last = (s == nsteps - 1);                                                       \
+    if (!last) { MRG_XLOAD(s + 1) }                                                            \
+    if (live) {                                                                                \
+      _Pragma("unroll")                                                                        \
+      for (int u = 0; u < 4; ++u) {                                                            \
+        _Pragma("unroll")                                                                      \
+        for (int t = 0; t < MT; ++t) {                                                         \
+          const bf16x8 b = *reinterpret_cast<const bf16x8*>(                                   \
+              xs + (BUF) * XIMG + (t * 32 + (lane & 31)) * XROW + u * 16 + (lane >> 5) * 8);   \
+          _Pragma("unroll")                                                                    \
+          for (int g = 0; g < NS; ++g)                                                         \
+            acc[g][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_buf[BUF][g][u], b,           \
+                                                                acc[g][t], 0, 0, 0);           \
+        }                                                                                      \
+      }                                                                                        \
+      if (s + 2 < nsteps) {                                                                    \
+        MRG_ALOAD(BUF, 0)                                                                      \
+        _Pragma("unroll")                                                                      \
+        for (int g = 0; g < NS; ++g) wp[g] += 4 * 512;                                         \
+      }                                                                                        \
+    }                                                                                          \
+    if (!last) {                                                                               \
+      MRG_XSTORE(1 - (BUF))                                                                    \
+      __syncthreads();                                                                         \
+    } else {                                                                                   \
+      asm volatile("s_nop 9\n\ts_nop 9");                                                      \
+    }                                                                                          \
+  }
+
+  int s = 0;
+  while (s + 2 <= nsteps) {
+    MRG_STEP(0);
+    ++s;
+    MRG_STEP(1);
+    ++s;
+  }
+  if (s < nsteps) MRG_STEP(0);
+#undef MRG_STEP
+#undef MRG_ALOAD
+#undef MRG_XLOAD
+#undef MRG_XSTORE
+
+  if (!live) return;
+  // D layout (skinny_store_acc): the lane holds slot row0 + 32 t + (lane & 31),
+  // columns cbase + 8 q + j of its tile, q, j = 0..3
+  const int cbase = j32 * 32 + 4 * (lane >> 5);
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int slot = row0 + t * 32 + (lane & 31);
+    if (slot >= rend) continue;
+    unsigned short* yrow = Y + (size_t)slot * NOUT + cbase;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      unsigned short o[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if constexpr (GLU) o[j] = swiglu_bf16(f2b(acc[0][t][q * 4 + j]), f2b(acc[1][t][q * 4 + j]));
+        else o[j] = f2b(acc[0][t][q * 4 + j]);
+      }
+      *reinterpret_cast<unsigned long long*>(yrow + q * 8) = *reinterpret_cast<unsigned long long*>(o);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // v3: packed-A + register-resident-X variant for the M=128/256 decode shapes.
 // The LDS-staged v2 wins at M<=64, but at MT>=4 its X staging doubles
 // (16 KB/step), the barrier pairs serialize the A stream, and the staging
@@ -4125,6 +4433,90 @@ torch::Tensor moe_combine(torch::Tensor y, torch::Tensor inv_pos, torch::Tensor 
   return out;
 }
 
+// Slots per tile of the ragged grouped GEMM: MT = 4 row tiles of 32. The plan
+// and the GEMM launcher both take it from here (python: MOE_RAGGED_BM).
+constexpr int MOE_RAGGED_MT = 4;
+constexpr int MOE_RAGGED_BM = MOE_RAGGED_MT * 32;
+
+// idx: [T, k] int32 expert choices -> (sorted_tok [A], inv_pos [T, k],
+// tile_expert [NB], tile_row0 [NB], offsets [E + 1]), all int32, A = T * k,
+// NB = ceil(A / BM) + E. Two launches over G = ceil(A / 512) <= 256 chunks.
+std::vector<torch::Tensor> moe_plan(torch::Tensor idx, int64_t E, int64_t BM) {
+  CHK(idx.is_cuda() && idx.dtype() == torch::kInt32 && idx.is_contiguous() && idx.dim() == 2);
+  const long long T = idx.size(0), k = idx.size(1), A = T * k;
+  TORCH_CHECK(E >= 1 && E <= 256, "moe_plan: E must be in 1..256, got ", E);
+  TORCH_CHECK(BM >= 32 && BM % 32 == 0, "moe_plan: BM must be a multiple of 32, got ", BM);
+  TORCH_CHECK(A >= 1 && A < (1LL << 24), "moe_plan: T * k must be in 1..2^24, got ", A);
+  const long long NB = (A + BM - 1) / BM + E;
+  const int G = (int)std::min<long long>(MOE_PLAN_MAXG, (A + MOE_PLAN_CHUNK - 1) / MOE_PLAN_CHUNK);
+  auto opts = torch::TensorOptions().dtype(torch::kInt32).device(idx.device());
+  auto block_counts = torch::empty({(long)G, (long)E}, opts);
+  auto sorted_tok = torch::empty({(long)A}, opts);
+  auto inv_pos = torch::empty({(long)T, (long)k}, opts);
+  auto tile_expert = torch::empty({(long)NB}, opts);
+  auto tile_row0 = torch::empty({(long)NB}, opts);
+  auto offsets = torch::empty({(long)E + 1}, opts);
+  hipLaunchKernelGGL(moe_plan_count_kernel, dim3(G), dim3(256), 0, cur_stream(),
+                     idx.data_ptr<int>(), block_counts.data_ptr<int>(), (int)A, (int)E);
+  hipLaunchKernelGGL(moe_plan_kernel, dim3(G), dim3(256), 0, cur_stream(),
+                     idx.data_ptr<int>(), block_counts.data_ptr<int>(), sorted_tok.data_ptr<int>(),
+                     inv_pos.data_ptr<int>(), tile_expert.data_ptr<int>(), tile_row0.data_ptr<int>(),
+                     offsets.data_ptr<int>(), (int)A, (int)k, (int)E, (int)BM, (int)NB);
+  return {sorted_tok, inv_pos, tile_expert, tile_row0, offsets};
+}
+
+// One projection of every expert over the dense sorted list of moe_plan (BM =
+// MOE_RAGGED_BM). wp: the stacked pack [E, N/32, K/16, 64, 8].
+//   gather && glu (gate_up): x = flat [T, K], N = 2I -> H [A, I] =
+//     silu(gate) * up of row sorted_tok[slot], the bits of swiglu_packed on the
+//     bf16 [A, 2I] product
+//   neither (down): x = H [A, K] -> Y [A, N]
+// Grid (n tiles, NB), n fastest: the NT workgroups of one table entry are
+// dispatched together, so its <= BM gathered X rows (BM * K * 2 B, 1 MB at
+// K = 4096) are fetched once per XCD and then hit in L2 while the entry sweeps
+// its expert's weights once; an expert's weights are streamed once per row
+// tile it has, and with many experts and m_e of a few tiles (qwen3-moe,
+// DeepSeek: the shapes this route is for) that is once or twice, with the row
+// tiles of one expert adjacent in y so their sweeps overlap in time. m fastest
+// would hold a 128-row weight tile (the same bytes as an X tile) across an
+// expert's row tiles instead, but neighbouring table entries belong to one
+// expert only inside long experts, and it re-gathers every X row NT times.
+torch::Tensor moe_gemm_ragged(torch::Tensor x, torch::Tensor wp, int64_t N, torch::Tensor sorted_tok,
+                              torch::Tensor tile_expert, torch::Tensor tile_row0, torch::Tensor offsets,
+                              bool gather, bool glu) {
+  TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.is_contiguous() && x.dim() == 2,
+              "moe_gemm_ragged: x must be a contiguous bf16 [rows, K] device tensor");
+  TORCH_CHECK(wp.is_cuda() && wp.dtype() == torch::kBFloat16 && wp.is_contiguous() && wp.dim() >= 2,
+              "moe_gemm_ragged: wp must be the stacked bf16 pack [E, N/32, K/16, 64, 8] "
+              "(fp8 and MXFP4 stacks are not served here)");
+  TORCH_CHECK(gather == glu, "moe_gemm_ragged: built for gate_up (gather and glu) and down (neither)");
+  for (const torch::Tensor* t : {&sorted_tok, &tile_expert, &tile_row0, &offsets})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kInt32 && t->is_contiguous() && t->dim() == 1,
+                "moe_gemm_ragged: the plan tensors are 1-d int32 device tensors");
+  const long long E = offsets.numel() - 1, K = x.size(1), A = sorted_tok.numel(), NB = tile_expert.numel();
+  TORCH_CHECK(E >= 1 && wp.size(0) == E, "moe_gemm_ragged: the plan has ", E, " experts, the pack ", wp.size(0));
+  TORCH_CHECK(N >= 32 && N % (glu ? 64 : 32) == 0, "moe_gemm_ragged: N % 32 (glu: I = N/2 % 32) != 0, N = ", N);
+  TORCH_CHECK(K >= 64 && K % 64 == 0, "moe_gemm_ragged: K % 64 != 0, K = ", K);
+  TORCH_CHECK(wp.size(1) == N / 32 && wp.numel() == E * N * K,
+              "moe_gemm_ragged: the pack is not [E, N/32, K/16, 64, 8] for N = ", N, ", K = ", K);
+  TORCH_CHECK(A >= 1 && tile_row0.numel() == NB && NB == (A + MOE_RAGGED_BM - 1) / MOE_RAGGED_BM + E,
+              "moe_gemm_ragged: the plan was not built for BM = ", MOE_RAGGED_BM);
+  TORCH_CHECK(gather || x.size(0) == A, "moe_gemm_ragged: x has ", x.size(0), " rows, the plan ", A, " slots");
+  TORCH_CHECK(NB <= 65535 && x.size(0) < (1LL << 31), "moe_gemm_ragged: too many tiles or rows");
+  const long long NOUT = glu ? N / 2 : N;
+  auto y = torch::empty({(long)A, (long)NOUT}, x.options());
+  const dim3 grid((unsigned)((NOUT + 127) / 128), (unsigned)NB);
+  dispatch_bool(glu, [&](auto gate_up) {
+    constexpr bool G = decltype(gate_up)::value;
+    hipLaunchKernelGGL((moe_gemm_ragged_kernel<MOE_RAGGED_MT, G, G>), grid, dim3(256), 0, cur_stream(),
+                       (const unsigned short*)wp.data_ptr(), (const unsigned short*)x.data_ptr(),
+                       (unsigned short*)y.data_ptr(), sorted_tok.data_ptr<int>(),
+                       tile_expert.data_ptr<int>(), tile_row0.data_ptr<int>(), offsets.data_ptr<int>(),
+                       (int)N, (int)K, (int)A, (int)x.size(0), (int)E);
+  });
+  return y;
+}
+
 // q: [B, S, H, nope+64] bf16 contiguous (raw projections, nope part is the
 // un-roped passthrough); q_lat: [B, S, H, 512] absorbed latent query;
 // positions [S] or [B * S]. Returns qfull with the roped 64-dim tail appended:
@@ -4930,6 +5322,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MoE decode routing: counting-sort token-expert pairs to padded per-expert slots");
   m.def("moe_combine", &moe_combine,
         "MoE decode combine: out[t] = sum_j w[t,j] * y[pos(t,j)] (deterministic)");
+  m.def("moe_plan", &moe_plan,
+        "MoE prefill plan: dense counting sort by expert + tile table of the ragged grouped GEMM");
+  m.def("moe_gemm_ragged", &moe_gemm_ragged,
+        "ragged grouped expert GEMM over a moe_plan: gate_up (gather + SwiGLU store) or down");
+  m.attr("MOE_RAGGED_BM") = (int)MOE_RAGGED_BM;
   m.def("mla_q_prep", &mla_q_prep,
         "MLA absorbed-query finisher: rope the 64-dim tail + assemble [B,H,576]; "
         "fp8=True returns (q8, per-head scales)",
