@@ -289,6 +289,8 @@ class ChatGPTAPI:
         state["temperature"] = float(chat_request.temperature)
       if data.get("top_p") is not None:
         state["top_p"] = float(data["top_p"])
+      if data.get("top_k") is not None:
+        state["top_k"] = int(data["top_k"])
       try:
         n_prompt = len(tokenizer.encode(prompt))
       except Exception:

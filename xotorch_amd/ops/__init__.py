@@ -541,3 +541,35 @@ def softmax_sample(logits, temperature: float = 0.0, top_k: int = 0, generator=N
                    top_p: float = 0.0):
   # torch ops here are graph-capturable (argmax / exponential+argmax)
   return torch_ref.softmax_sample(logits, temperature, top_k, generator, top_p)
+
+
+def hip_sample_enabled() -> bool:
+  """XOT_HIP_SAMPLE (default 0, read per call): the serve ring's last rank
+  samples every slot in one ops.sample launch from per-slot device tensors of
+  temperature, top-k and top-p; 0 keeps the per-slot softmax_sample loop."""
+  return os.getenv("XOT_HIP_SAMPLE", "0") == "1"
+
+
+def _per_row(v, B: int, dtype: torch.dtype, device) -> torch.Tensor:
+  if isinstance(v, torch.Tensor):
+    return v.to(device=device, dtype=dtype).expand(B).contiguous()
+  return torch.full((B,), v, dtype=dtype, device=device)
+
+
+def sample(logits, temperature, top_k=0, top_p=0.0, u=None, generator=None, out=None):
+  """Per-row temperature / top-k / top-p sampling of logits [B, V] with one
+  uniform per row (torch_ref.sample states the definition) -> int64 [B].
+  temperature, top_k and top_p are scalars or [B] tensors: top_k outside
+  (0, V) and top_p outside (0, 1) are off, temperature <= 1e-4 is greedy.
+  u [B] in [0, 1) is drawn from `generator` when None. On the GPU one
+  sample_rows launch, bf16 or fp32 logits; `out` receives the tokens."""
+  B, dev = logits.shape[0], logits.device
+  temperature = _per_row(temperature, B, torch.float32, dev)
+  top_k = _per_row(top_k, B, torch.int32, dev)
+  top_p = _per_row(top_p, B, torch.float32, dev)
+  if u is None:
+    u = torch.rand(B, device=dev, generator=generator)
+  if _use_hip(logits):
+    return _hip.sample_rows(logits.contiguous(), temperature, top_k, top_p, u, out)
+  tok = torch_ref.sample(logits, temperature, top_k, top_p, u)
+  return tok if out is None else out.copy_(tok)

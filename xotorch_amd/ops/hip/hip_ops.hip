@@ -1459,6 +1459,276 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Token sampling: per-row temperature, top-k, top-p and one inverse-CDF draw
+// in one launch over logits [B, V] (bf16 or fp32), parameters read per row
+// from device tensors. One workgroup of 1024 threads owns a row; the row is
+// read from L2 once per pass, 16 B per lane.
+//
+//   pass 0   row max and lowest argmax; a greedy row (T <= 1e-4) ends here
+//   select   v_k and the top-p cut are thresholds on the order-preserving
+//            integer key of the logit, found by radix select, SAMPLE_LB key
+//            bits per pass from the top (bf16 12 + 4, fp32 12 + 12 + 8): an
+//            LDS histogram of the elements under the prefix fixed so far,
+//            scanned from its top bin for the first bin where the running sum
+//            passes the limit. top-k adds 1 per element (limit k - 1), top-p
+//            adds the element's mass over the top-k survivors (limit p * W_k,
+//            W_k = that histogram's total)
+//   draw     tile sums (a tile = the 64 x 16 B one wave loads at once, in
+//            index order) into the same LDS, the same scan for the tile that
+//            holds u * W', then one wave scans that tile and one lane walks
+//            its 16 B
+//
+// A mass is w = exp((l - max) / T) truncated to a multiple of 2^-40 in a
+// 64-bit integer: integer adds do not depend on the order LDS atomics arrive
+// in, so every cut and the drawn token are reproducible, and every comparison
+// is exact given the w. An element with (l - max) / T < -28 has w = 0 and is
+// skipped outright: all of them sit below every element that carries mass, so
+// they can only be kept or dropped together, and none can be drawn.
+// ---------------------------------------------------------------------------
+
+constexpr int SAMPLE_THREADS = 1024;
+constexpr int SAMPLE_LB = 12;             // key bits per select pass
+constexpr int SAMPLE_NB = 1 << SAMPLE_LB;  // histogram bins = most tiles of a row
+constexpr float SAMPLE_DEAD = -28.f;       // exp(-28) < 2^-40
+constexpr float SAMPLE_ONE = 1099511627776.f;  // 2^40
+typedef unsigned long long u64;
+
+template <typename T> struct SampleElem;
+template <> struct SampleElem<__hip_bfloat16> {
+  typedef unsigned short Bits;
+  typedef ushort8 Vec;
+  static constexpr int VEC = 8, KEYBITS = 16;
+  static DEVINL float value(unsigned int b) { return b2f((unsigned short)b); }
+};
+template <> struct SampleElem<float> {
+  typedef unsigned int Bits;
+  typedef uintx4 Vec;
+  static constexpr int VEC = 4, KEYBITS = 32;
+  static DEVINL float value(unsigned int b) { return __uint_as_float(b); }
+};
+
+// order-preserving key of a float's bits (-0 counts as +0) and its inverse
+template <int KEYBITS>
+DEVINL unsigned int sample_key(unsigned int b) {
+  constexpr unsigned int SIGN = 1u << (KEYBITS - 1), ALL = SIGN | (SIGN - 1);
+  if (b == SIGN) b = 0;
+  return (b & SIGN) ? (~b & ALL) : (b | SIGN);
+}
+template <int KEYBITS>
+DEVINL unsigned int sample_unkey(unsigned int k) {
+  constexpr unsigned int SIGN = 1u << (KEYBITS - 1), ALL = SIGN | (SIGN - 1);
+  return (k & SIGN) ? (k & ~SIGN) : (~k & ALL);
+}
+
+DEVINL u64 shfl_xor_u64(u64 v, int m) {
+  return ((u64)__shfl_xor((unsigned int)(v >> 32), m) << 32) | __shfl_xor((unsigned int)v, m);
+}
+DEVINL u64 shfl_up_u64(u64 v, int d) {
+  return ((u64)__shfl_up((unsigned int)(v >> 32), d) << 32) | __shfl_up((unsigned int)v, d);
+}
+DEVINL u64 wave_incl_scan_u64(u64 v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const u64 o = shfl_up_u64(v, d);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+
+// Unit u of a row = the 16 B at virtual indices [u * VEC, (u + 1) * VEC), where
+// virtual index = index + shift and shift makes unit 0 start 16 B aligned. A
+// unit inside the row is one vector load; the two edge units load by element.
+// f(j, index, bits) on the elements of the unit that the row has.
+template <typename E, typename F>
+DEVINL void sample_visit(const typename E::Bits* __restrict__ row, int V, int shift, int u, F&& f) {
+  const int i0 = u * E::VEC - shift;
+  if (i0 >= 0 && i0 + E::VEC <= V) {
+    const typename E::Vec v = *reinterpret_cast<const typename E::Vec*>(row + i0);
+#pragma unroll
+    for (int j = 0; j < E::VEC; ++j) f(j, i0 + j, (unsigned int)v[j]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < E::VEC; ++j)
+      if (i0 + j >= 0 && i0 + j < V) f(j, i0 + j, (unsigned int)row[i0 + j]);
+  }
+}
+
+DEVINL u64 sample_mass(float l, float lmax, float inv_t) {
+  const float d = (l - lmax) * inv_t;
+  return d < SAMPLE_DEAD ? 0ull : (u64)(expf(d) * SAMPLE_ONE);
+}
+
+struct SampleShared {
+  u64 hist[SAMPLE_NB];
+  u64 wave_tot[SAMPLE_THREADS / 64];
+  u64 above;
+  int bin;
+};
+
+// The first bin b from the top with above(b) + hist[b] > limit, above(b) = the sum
+// of the bins over b; false when the whole histogram does not pass the limit.
+// With frac >= 0 the limit is floor(frac * total) and is returned. Every thread
+// calls it and gets the same answer; hist is free to overwrite on return.
+DEVINL bool sample_scan_top(SampleShared& sh, double frac, u64& limit, int& bin, u64& above) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int PER = SAMPLE_NB / SAMPLE_THREADS;
+  const int top = SAMPLE_NB - 1 - tid * PER;
+  u64 h[PER], mine = 0;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) { h[j] = sh.hist[top - j]; mine += h[j]; }
+  const u64 incl = wave_incl_scan_u64(mine, lane);
+  if (lane == 63) sh.wave_tot[wave] = incl;
+  if (tid == 0) sh.bin = -1;
+  __syncthreads();
+  u64 a = incl - mine, total = 0;
+#pragma unroll
+  for (int w = 0; w < SAMPLE_THREADS / 64; ++w) {
+    const u64 t = sh.wave_tot[w];
+    if (w < wave) a += t;
+    total += t;
+  }
+  if (frac >= 0.0) limit = (u64)(frac * (double)total);
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    if (a <= limit && a + h[j] > limit) { sh.bin = top - j; sh.above = a; }  // one bin in the row
+    a += h[j];
+  }
+  __syncthreads();
+  bin = sh.bin;
+  above = sh.above;
+  __syncthreads();
+  return bin >= 0;
+}
+
+// Radix select over the elements with key >= floor_key that carry mass: the key
+// t of the first value class from the top at which the running sum passes the
+// limit (MASS false: 1 per element, limit = k - 1, so t = the k-th largest;
+// MASS true: the element's mass, limit = floor(p * total), so the classes above
+// t hold at most p of the total and with t they hold more). 0 = keep everything.
+template <typename E, bool MASS>
+DEVINL unsigned int sample_select(SampleShared& sh, const typename E::Bits* __restrict__ row, int V,
+                                  int shift, int n_units, unsigned int floor_key, float lmax,
+                                  float inv_t, u64 limit, double frac) {
+  const int tid = threadIdx.x;
+  unsigned int prefix = 0;
+  for (int pbits = 0; pbits < E::KEYBITS;) {
+    const int bits = min(SAMPLE_LB, E::KEYBITS - pbits), down = E::KEYBITS - pbits - bits;
+    for (int i = tid; i < SAMPLE_NB; i += SAMPLE_THREADS) sh.hist[i] = 0;
+    __syncthreads();
+    for (int u = tid; u < n_units; u += SAMPLE_THREADS)
+      sample_visit<E>(row, V, shift, u, [&](int, int, unsigned int b) {
+        const unsigned int key = sample_key<E::KEYBITS>(b);
+        if (key < floor_key || (pbits && (key >> (E::KEYBITS - pbits)) != prefix)) return;
+        u64 add;
+        if (MASS) add = sample_mass(E::value(b), lmax, inv_t);
+        else add = (E::value(b) - lmax) * inv_t < SAMPLE_DEAD ? 0 : 1;
+        if (add) atomicAdd(&sh.hist[(key >> down) & ((1u << bits) - 1)], add);
+      });
+    __syncthreads();
+    int bin;
+    u64 above;
+    if (!sample_scan_top(sh, pbits == 0 ? frac : -1.0, limit, bin, above)) return 0;
+    limit -= above;
+    prefix = (prefix << bits) | (unsigned int)bin;
+    pbits += bits;
+  }
+  return prefix;
+}
+
+template <typename T>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(
+    const T* __restrict__ logits, const float* __restrict__ temperature,
+    const int* __restrict__ top_k, const float* __restrict__ top_p,
+    const float* __restrict__ uniform, long long* __restrict__ tokens, int V) {
+  typedef SampleElem<T> E;
+  __shared__ SampleShared sh;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x;
+  const typename E::Bits* row = reinterpret_cast<const typename E::Bits*>(logits) + (size_t)b * V;
+  const int shift = (int)(((uintptr_t)row & 15) / sizeof(typename E::Bits));
+  const int n_units = (V + shift + E::VEC - 1) / E::VEC;
+
+  // pass 0: (key, ~index) packed, so the max is the largest logit at its lowest index
+  u64 best = 0;
+  for (int u = tid; u < n_units; u += SAMPLE_THREADS)
+    sample_visit<E>(row, V, shift, u, [&](int, int i, unsigned int bits) {
+      const u64 c = ((u64)sample_key<E::KEYBITS>(bits) << 32) | (0xffffffffu - (unsigned int)i);
+      best = c > best ? c : best;
+    });
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+    const u64 o = shfl_xor_u64(best, m);
+    best = o > best ? o : best;
+  }
+  if (lane == 0) sh.wave_tot[wave] = best;
+  __syncthreads();
+  for (int w = 0; w < SAMPLE_THREADS / 64; ++w) best = sh.wave_tot[w] > best ? sh.wave_tot[w] : best;
+  __syncthreads();
+  const long long argmax = (long long)(0xffffffffu - (unsigned int)best);
+  const float temp = temperature[b];
+  if (!(temp > 1e-4f)) {  // greedy; also what an idle slot's zeroed parameters give
+    if (tid == 0) tokens[b] = argmax;
+    return;
+  }
+  const float lmax = E::value(sample_unkey<E::KEYBITS>((unsigned int)(best >> 32)));
+  const float inv_t = 1.f / temp;
+  const int k = top_k[b];
+  const float p = top_p[b];
+
+  unsigned int keep_key = 0;  // the kept set is key >= keep_key
+  if (k > 0 && k < V)
+    keep_key = sample_select<E, false>(sh, row, V, shift, n_units, 0, lmax, inv_t, (u64)(k - 1), -1.0);
+  if (p > 0.f && p < 1.f) {
+    const unsigned int cut = sample_select<E, true>(sh, row, V, shift, n_units, keep_key, lmax, inv_t, 0, (double)p);
+    keep_key = cut > keep_key ? cut : keep_key;
+  }
+
+  // draw: tile t = units [64 t, 64 t + 64) sits in hist[NB - 1 - t], so the scan
+  // from the top runs in index order
+  const int n_tiles = (n_units + 63) >> 6;
+  for (int i = tid; i < SAMPLE_NB; i += SAMPLE_THREADS) sh.hist[i] = 0;
+  __syncthreads();
+  u64 each[E::VEC];  // the kept masses of one unit
+  auto unit_mass = [&](int u) {
+#pragma unroll
+    for (int j = 0; j < E::VEC; ++j) each[j] = 0;
+    if (u < n_units)
+      sample_visit<E>(row, V, shift, u, [&](int j, int, unsigned int bits) {
+        if (sample_key<E::KEYBITS>(bits) >= keep_key) each[j] = sample_mass(E::value(bits), lmax, inv_t);
+      });
+    u64 sum = 0;
+#pragma unroll
+    for (int j = 0; j < E::VEC; ++j) sum += each[j];
+    return sum;
+  };
+  for (int t = wave; t < n_tiles; t += SAMPLE_THREADS / 64) {
+    u64 s = unit_mass(t * 64 + lane);
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) s += shfl_xor_u64(s, m);
+    if (lane == 0) sh.hist[SAMPLE_NB - 1 - t] = s;
+  }
+  __syncthreads();
+  u64 limit = 0, above;
+  int bin;
+  if (!sample_scan_top(sh, (double)uniform[b], limit, bin, above)) {
+    if (tid == 0) tokens[b] = argmax;  // no mass at all (a row of NaN): never out of range
+    return;
+  }
+  if (wave != 0) return;
+  const u64 rem = limit - above;  // the draw inside the tile
+  const int u = (SAMPLE_NB - 1 - bin) * 64 + lane;
+  const u64 mine = unit_mass(u);
+  u64 c = wave_incl_scan_u64(mine, lane) - mine;
+  if (c <= rem && c + mine > rem) {
+#pragma unroll
+    for (int j = 0; j < E::VEC; ++j) {
+      if (c <= rem && c + each[j] > rem) tokens[b] = (long long)(u * E::VEC - shift + j);
+      c += each[j];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // MLA (DeepSeek V2/V3) decode attention on matrix cores — ABSORBED form.
 //
 // The kv_b projection is folded into the query and output (DeepSeek's own
@@ -4433,6 +4703,39 @@ torch::Tensor moe_combine(torch::Tensor y, torch::Tensor inv_pos, torch::Tensor 
   return out;
 }
 
+// logits [B, V] bf16 | fp32, per-row temperature fp32, top_k int32, top_p fp32 and
+// uniform u fp32 in [0, 1), all [B] -> token ids int64 [B] (sample_rows_kernel;
+// top_k outside (0, V) and top_p outside (0, 1) are off, temperature <= 1e-4 is
+// greedy). No host sync; `out` makes it allocation-free.
+torch::Tensor sample_rows(torch::Tensor logits, torch::Tensor temperature, torch::Tensor top_k,
+                          torch::Tensor top_p, torch::Tensor u, c10::optional<torch::Tensor> out) {
+  CHK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous());
+  CHK(logits.dtype() == torch::kBFloat16 || logits.dtype() == torch::kFloat32);
+  const long long B = logits.size(0), V = logits.size(1);
+  const bool bf16 = logits.dtype() == torch::kBFloat16;
+  CHK(B >= 1 && V >= 1 && V / (bf16 ? 8 : 4) + 2 <= (long long)SAMPLE_NB * 64);  // a tile sum per histogram bin
+  auto per_row = [&](const torch::Tensor& t, c10::ScalarType dt) {
+    return t.device() == logits.device() && t.dtype() == dt && t.dim() == 1 && t.size(0) == B && t.is_contiguous();
+  };
+  CHK(per_row(temperature, torch::kFloat32) && per_row(top_k, torch::kInt32));
+  CHK(per_row(top_p, torch::kFloat32) && per_row(u, torch::kFloat32));
+  torch::Tensor tokens;
+  if (out.has_value()) {
+    CHK(per_row(*out, torch::kInt64));
+    tokens = *out;
+  } else {
+    tokens = torch::empty({B}, torch::TensorOptions().dtype(torch::kInt64).device(logits.device()));
+  }
+  auto launch = [&](auto* lp) {
+    hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, cur_stream(), lp,
+                       temperature.data_ptr<float>(), top_k.data_ptr<int>(), top_p.data_ptr<float>(),
+                       u.data_ptr<float>(), (long long*)tokens.data_ptr<int64_t>(), (int)V);
+  };
+  if (bf16) launch((const __hip_bfloat16*)logits.data_ptr());
+  else launch((const float*)logits.data_ptr<float>());
+  return tokens;
+}
+
 // Slots per tile of the ragged grouped GEMM: MT = 4 row tiles of 32. The plan
 // and the GEMM launcher both take it from here (python: MOE_RAGGED_BM).
 constexpr int MOE_RAGGED_MT = 4;
@@ -5318,6 +5621,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("logits"), py::arg("bias") = py::none(), py::arg("k") = 2,
         py::arg("mode") = 0, py::arg("n_group") = 1, py::arg("topk_group") = 1,
         py::arg("routed_scale") = 1.0, py::arg("norm_topk") = false);
+  m.def("sample_rows", &sample_rows,
+        "per-row temperature / top-k / top-p sampling of logits [B, V] in one launch -> int64 [B]",
+        py::arg("logits"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"), py::arg("u"),
+        py::arg("out") = py::none());
   m.def("moe_build", &moe_build,
         "MoE decode routing: counting-sort token-expert pairs to padded per-expert slots");
   m.def("moe_combine", &moe_combine,

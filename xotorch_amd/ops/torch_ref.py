@@ -328,3 +328,38 @@ def softmax_sample(
   probs = torch.softmax(logits, dim=-1)
   q = torch.empty_like(probs).exponential_(1, generator=generator)
   return (probs / q).argmax(dim=-1)
+
+
+def sample_kept(logits, temperature, top_k, top_p):
+  """The definition ops.sample implements, in float64: logits [B, V] and per-row
+  temperature, top_k, top_p [B] -> (keep bool [B, V], w float64 [B, V], greedy
+  bool [B]). w = exp((l - max) / T). top-k (0 < k < V) keeps l >= the k-th
+  largest logit, ties included. top-p (0 < p < 1) then keeps i iff G(l_i) <=
+  p * W_k, with G(v) the mass of the logits strictly above v and W_k the mass
+  of the top-k survivors: whole value classes, never a sort order among equals."""
+  V = logits.shape[-1]
+  l = logits.double()
+  greedy = temperature <= 1e-4
+  t = torch.where(greedy, torch.ones_like(temperature), temperature).double()
+  w = torch.exp((l - l.amax(-1, keepdim=True)) / t[:, None])
+  sl, order = torch.sort(l, dim=-1, descending=True)
+  k = torch.where((top_k > 0) & (top_k < V), top_k, torch.full_like(top_k, V)).long()
+  keep = l >= sl.gather(1, k[:, None] - 1)
+  w_k = (w * keep).sum(-1)
+  # G: the mass before the first sorted position that holds the same value
+  cum = F.pad(w.gather(1, order).cumsum(-1), (1, 0))
+  above = cum.gather(1, torch.searchsorted(-sl, -l.contiguous()))
+  p_on = (top_p > 0) & (top_p < 1)
+  keep &= ~p_on[:, None] | (above <= (top_p.double() * w_k)[:, None])
+  return keep, w, greedy
+
+
+def sample(logits, temperature, top_k, top_p, u):
+  """Per-row temperature / top-k / top-p sampling with one uniform u [B] in
+  [0, 1) per row: the token is the smallest kept index whose running kept mass,
+  in index order, exceeds u * (kept mass). A row with temperature <= 1e-4 takes
+  its lowest argmax. -> token ids int64 [B]."""
+  keep, w, greedy = sample_kept(logits, temperature, top_k, top_p)
+  c = (w * keep).cumsum(-1)
+  hit = keep & (c > (u.double() * c[:, -1])[:, None])
+  return torch.where(greedy, logits.argmax(-1), hit.to(torch.uint8).argmax(-1))

@@ -20,7 +20,7 @@ RCCL/xGMI, and requests are served with SLOT-BASED CONTINUOUS BATCHING:
   a thin Node adapter.
 
 Control plane per tick: rank 0 broadcasts a small header (op, slot, len,
-milli-temperature); ADMIT is followed by the prompt tokens; the last stage
+milli-temperature with top-p and top-k packed above it); ADMIT is followed by the prompt tokens; the last stage
 samples and broadcasts the per-slot tokens; rank 0 streams them to clients.
 All collectives go through RingComm, so N ranks verify on fewer GPUs (gloo
 staging) while the real deployment runs pure RCCL.
@@ -57,6 +57,22 @@ OP_IDLE, OP_DECODE, OP_ADMIT, OP_RELEASE, OP_SHUTDOWN, OP_PREFILL = 0, 1, 2, 3, 
 MAX_SEQ = int(os.getenv("XOT_SERVE_MAX_SEQ", "4096"))
 SLOTS = int(os.getenv("XOT_SERVE_SLOTS", "8"))
 PREFILL_CHUNK = int(os.getenv("XOT_SERVE_PREFILL_CHUNK", "256"))
+DEFAULT_TOP_K = 35  # applies when a request names no top_k
+
+
+def pack_sample_word(temp: float, top_p: float = 0.0, top_k: int = 0) -> int:
+  """The admit header's fourth word: milli-temperature in the low 20 bits,
+  top-p in thousandths in the 10 above (0 = off), top-k above that (0 = the
+  request named none). Temperature alone gives int(temp * 1000)."""
+  p = float(top_p or 0.0)
+  return (min(int(temp * 1000), (1 << 20) - 1)
+          | (int(round(p * 1000)) if 0.0 < p < 1.0 else 0) << 20
+          | max(int(top_k or 0), 0) << 30)
+
+
+def unpack_sample_word(word: int):
+  """-> (temperature, top_p, top_k)."""
+  return (word & ((1 << 20) - 1)) / 1000.0, ((word >> 20) & 1023) / 1000.0, word >> 30
 
 
 @dataclass
@@ -66,6 +82,8 @@ class SlotState:
   generated: int = 0
   max_new: int = 0
   temp: float = 0.0
+  top_p: float = 0.0
+  top_k: int = DEFAULT_TOP_K
   done: bool = False  # finished but not yet released (release is its own tick)
   ttft_s: float = 0.0
   t_admit: float = 0.0
@@ -78,6 +96,8 @@ class AdmitMsg:
   max_new: int
   temp: float
   t_submit: float = field(default_factory=time.perf_counter)
+  top_p: float = 0.0  # 0 or >= 1: off
+  top_k: int = 0      # 0: DEFAULT_TOP_K
 
 
 class RingSlotWorker:
@@ -127,6 +147,14 @@ class RingSlotWorker:
     self._pf: Dict[int, dict] = {}  # slot -> in-progress chunked prefill (every rank)
     self._pf_turn = False
     self.eos_token_id = self.cfg.eos_token_id
+    # XOT_HIP_SAMPLE=1: per-slot sampling parameters the one ops.sample launch
+    # reads, written at admit and zeroed at release (a zero row is greedy)
+    self.samp_temp = torch.zeros(slots, dtype=torch.float32, device=dev)
+    self.samp_top_k = torch.zeros(slots, dtype=torch.int32, device=dev)
+    self.samp_top_p = torch.zeros(slots, dtype=torch.float32, device=dev)
+    self.samp_u = torch.zeros(slots, dtype=torch.float32, device=dev)
+    self.samp_gen = torch.Generator(device=dev)
+    self.samp_gen.manual_seed(int(os.getenv("XOT_SEED", "1234")))
 
   # ---------------- decode tick ----------------
 
@@ -197,6 +225,11 @@ class RingSlotWorker:
   def _sample_all(self):
     from xotorch_amd import ops
     logits = self.logits_buf  # [slots, V]
+    if ops.hip_sample_enabled():
+      torch.rand(self.slots, generator=self.samp_gen, out=self.samp_u)
+      ops.sample(logits, self.samp_temp, self.samp_top_k, self.samp_top_p, u=self.samp_u,
+                 out=self.tok_bcast)
+      return
     greedy = logits.argmax(dim=-1)
     toks = greedy
     temps = [self.slot_state[i].temp for i in range(self.slots)]
@@ -234,8 +267,11 @@ class RingSlotWorker:
         return None
       st = self.slot_state[slot]
       logits = h[:, -1] if h.dim() == 3 else h
+      from xotorch_amd import ops
+      if ops.hip_sample_enabled():
+        return int(ops.sample(logits, self.samp_temp[slot:slot + 1], self.samp_top_k[slot:slot + 1],
+                              self.samp_top_p[slot:slot + 1], generator=self.samp_gen)[0])
       if st.temp > 0:
-        from xotorch_amd import ops
         return int(ops.softmax_sample(logits, temperature=st.temp, top_k=35)[0])
       return int(logits.argmax(dim=-1)[0])
 
@@ -317,7 +353,7 @@ class RingSlotWorker:
             op = OP_SHUTDOWN
           elif msg is not None:
             op, slot, plen = OP_ADMIT, free, msg.tokens.shape[1]
-            extra = int(msg.temp * 1000)
+            extra = pack_sample_word(msg.temp, msg.top_p, msg.top_k)
             inflight[free] = msg
           elif self._pf and (self._pf_turn or not any(self.active)):
             # alternate one prompt chunk with one decode tick so slots that
@@ -351,6 +387,8 @@ class RingSlotWorker:
             self.active[i] = False
             self.slot_state[i] = SlotState()
             self._pf.pop(i, None)
+            if self.is_last:
+              self.samp_temp[i], self.samp_top_k[i], self.samp_top_p[i] = 0.0, 0, 0.0
         self._reset_inactive()
         continue
       if op == OP_ADMIT:
@@ -361,8 +399,11 @@ class RingSlotWorker:
           toks = torch.zeros(1, plen, dtype=torch.int64, device=self.device)
         if self.world > 1:
           self.comm.broadcast(toks, 0)
-        st = SlotState(prompt_len=plen, temp=extra / 1000.0)
+        temp, top_p, top_k = unpack_sample_word(extra)
+        st = SlotState(prompt_len=plen, temp=temp, top_p=top_p, top_k=top_k or DEFAULT_TOP_K)
         self.slot_state[slot] = st
+        if self.is_last:
+          self.samp_temp[slot], self.samp_top_k[slot], self.samp_top_p[slot] = st.temp, st.top_k, st.top_p
         self._pf[slot] = {"toks": toks, "c0": 0, "plen": plen,
                           "caches": self._slot_caches(slot)}
         if self.rank == 0:
@@ -490,7 +531,8 @@ class RingAPINode:
     tokens = torch.tensor([ids], dtype=torch.int64)
     max_new = int(state.get("max_tokens") or 256)
     temp = float(state.get("temperature") or 0.0)
-    self.admit_q.put(AdmitMsg(request_id, tokens, max_new, temp))
+    self.admit_q.put(AdmitMsg(request_id, tokens, max_new, temp, top_p=float(state.get("top_p") or 0.0),
+                              top_k=int(state.get("top_k") or 0)))
     return request_id
 
 
