@@ -57,10 +57,10 @@ class Attention(nn.Module):
 
   def _forward_nocache(self, x, cos, sin, positions):
     """Cache-free causal attention (training/eval): the SAME modules and
-    weights as the inference path, autograd-safe ops (fp32 sdpa). This is
+    weights as the inference path, autograd-safe ops (fp32 sdpa; under
+    XOT_TRAIN_ATTN=1, bf16 on the GPU, the attn_train kernels). This is
     the one and only training forward — the engine calls the model, so the
     two paths cannot drift (round-1 VERDICT weak #7)."""
-    import torch.nn.functional as F
     B, S, _ = x.shape
     cfg = self.cfg
     H, KVH, hd = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
@@ -74,14 +74,11 @@ class Attention(nn.Module):
       q = tr.rmsnorm(q.float(), self.q_norm.float(), cfg.norm_eps).to(q.dtype)
       k = tr.rmsnorm(k.float(), self.k_norm.float(), cfg.norm_eps).to(k.dtype)
     q, k = ops.rope_apply(q, k, cos, sin, positions)
-    rep = H // KVH
-    out = F.scaled_dot_product_attention(
-      q.transpose(1, 2).float(),
-      k.transpose(1, 2).repeat_interleave(rep, dim=1).float(),
-      v.transpose(1, 2).repeat_interleave(rep, dim=1).float(),
-      is_causal=True,
-    ).to(x.dtype)
-    return self.o_proj(out.transpose(1, 2).reshape(B, S, H * hd))
+    if ops.attn_train_enabled() and x.is_cuda and x.dtype == torch.bfloat16 and ops.attn_train_fits(H, KVH, hd):
+      out = ops.attn_train(q, k, v)  # XOT_TRAIN_ATTN=1: flash forward / backward kernels, v read in place
+    else:
+      out = ops.torch_ref.attn_train(q, k, v)
+    return self.o_proj(out.reshape(B, S, H * hd))
 
   def forward(self, x, cos, sin, positions, kv, start_pos: int, is_decode: bool, seq_lens=None):
     if kv is None:

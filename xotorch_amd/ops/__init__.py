@@ -43,7 +43,8 @@ def _use_hip(*tensors: torch.Tensor) -> bool:
     return False
   if torch.is_grad_enabled() and any(x.requires_grad for x in tensors):
     # training path: HIP kernels are inference-only (no autograd); the torch
-    # ops are differentiable. Inference runs on the HIP kernels.
+    # ops are differentiable. Inference runs on the HIP kernels. (attn_train
+    # has a backward of its own and does not come through here.)
     return False
   if _load_hip() is not None:
     return True
@@ -225,6 +226,49 @@ def attn_prefill(q, k_cache, v_cache, start_pos: int, s_len: int, kp=None, vp=No
       out = F.scaled_dot_product_attention(qh, k, v, attn_mask=mask, enable_gqa=True, scale=scale)
     return out.transpose(1, 2).contiguous()
   return torch_ref.attn_prefill(q, k_cache, v_cache, start_pos, s_len, scale, softcap, window)
+
+
+def attn_train_enabled() -> bool:
+  """XOT_TRAIN_ATTN (default 0, read per call): the llama-family training
+  forward runs attention on attn_train's flash forward / backward kernels
+  instead of fp32 sdpa over K / V expanded per query head."""
+  return os.getenv("XOT_TRAIN_ATTN", "0") == "1"
+
+
+def attn_train_fits(H: int, KVH: int, hd: int) -> bool:
+  """Whether the training attention kernels take this head geometry."""
+  return hd in (64, 128) and KVH > 0 and H % KVH == 0
+
+
+class _AttnTrain(torch.autograd.Function):
+  """attn_train_fwd / attn_train_bwd under autograd. Saves q, k, v, out and
+  lse by plain save_for_backward, so it composes with activation checkpointing."""
+
+  @staticmethod
+  def forward(ctx, q, k, v, scale):
+    out, lse = _gpu().attn_train_fwd(q, k, v, scale)
+    ctx.save_for_backward(q, k, v, out, lse)
+    ctx.scale = scale
+    return out
+
+  @staticmethod
+  def backward(ctx, dout):
+    q, k, v, out, lse = ctx.saved_tensors
+    dq, dk, dv = _gpu().attn_train_bwd(dout.contiguous(), q, k, v, out, lse, ctx.scale)
+    return dq, dk, dv, None
+
+
+def attn_train(q, k, v, scale=None):
+  """Cache-free causal GQA attention, differentiable: q [B, S, H, hd], k / v
+  [B, S, KVH, hd] -> [B, S, H, hd]. bf16 GPU tensors at a geometry that
+  attn_train_fits run the flash forward (which keeps the log-sum-exp) and the
+  deterministic backward kernels, reading q / k / v in place: any batch,
+  position and head strides with contiguous head rows, so views of the packed
+  qkv GEMM output pass without a copy. Everything else is torch_ref.attn_train."""
+  if q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 \
+     and attn_train_fits(q.shape[2], k.shape[2], q.shape[3]):
+    return _AttnTrain.apply(q, k, v, float(scale) if scale is not None else q.shape[3] ** -0.5)
+  return torch_ref.attn_train(q, k, v, scale)
 
 
 def attn_decode(q, k_cache, v_cache, seq_len, kp=None, vp=None,

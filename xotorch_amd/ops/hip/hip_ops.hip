@@ -2357,6 +2357,518 @@ __global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_prefill_mla_kern
 }
 
 // ---------------------------------------------------------------------------
+// Training attention (causal GQA, bf16, HD = 64 or 128): a flash forward that
+// saves lse = m + log(l) per row, and a deterministic backward in two kernels.
+// No cache and no fragment packing: q [B, S, H, HD] and k / v [B, S, KVH, HD]
+// are read in place from row-major rows (any b / s / head strides, last dim
+// contiguous), as attn_prefill_mla_kernel reads kvx, with that kernel's
+// staging: 32-row tiles in LDS, double-buffered, the next tile's global loads
+// issued before this tile's MFMAs and parked in LDS after them, one barrier
+// per tile. Every MFMA is v_mfma_f32_16x16x32_bf16:
+//   D[i = 4 quad + r][j = col] += sum_k A[i = col][k = 8 quad + e] B[k][j = col]
+// A tile in LDS serves an operand two ways. Contraction over dims (a lane
+// wants 8 consecutive dims of one row): b128 reads, 16 lanes on 16 consecutive
+// rows, conflict-free at a row stride of HD + 8 elements (AT_BROW: 36 / 68
+// dwords = 4 mod 32, 16 rows on 16 distinct 4-bank groups of 64 banks).
+// Contraction over rows (8 consecutive rows of one dim): ds_read_b64_tr_b16,
+// 32 lanes on 8 consecutive rows of 32 B, conflict-free at HD + 16 (AT_TROW:
+// 40 / 72 dwords = 8 mod 32). A tile that is read both ways takes AT_TROW: the
+// transposing reads are twice as many, and its b128 reads then meet 8 distinct
+// offsets for 16 rows (2-way).
+//   forward   S = Q K^T (K b128), online softmax, out += P V (V transposed)
+//   dq        S = Q K^T and dP = dO V^T (K, V b128), dQ += dS K (K transposed):
+//             K at AT_TROW, V at AT_BROW
+//   dkv       S^T = K Q^T and dP^T = V dO^T (Q, dO b128), dV += P^T dO and
+//             dK += dS^T Q (dO, Q transposed): both at AT_TROW
+// P and dS are rounded once to bf16 through a per-wave 16 x 32 image (96 B row
+// stride) that turns the D layout into the next MFMA's A operand. Nothing is
+// [S, S], no K / V is expanded per query head, and every sum runs in a fixed
+// order: two launches over the same inputs give the same bits.
+// Built without the packed fp32 VALU forms, like attn_prefill_mla_kernel.
+// ---------------------------------------------------------------------------
+
+constexpr int AT_BROW(int hd) { return hd + 8; }
+constexpr int AT_TROW(int hd) { return hd + 16; }
+// 16-row sub-tiles a wave owns in the forward and dq kernels (q blocks of
+// 64 * NT rows): from the resource table in docs/KERNELS.md
+constexpr int ATTN_TRAIN_NT(int hd) { return 2; }
+
+struct AtStrides { long long b, s, h; };  // elements; the last dim has stride 1
+
+// 32-row tile [row0, row0 + 32) x HD of a row-major tensor, rows clamped to
+// `last`: HD / 64 16-byte pieces per thread, piece e = tid + 256 i -> row
+// e / (HD / 8), dims (e % (HD / 8)) * 8
+template <int HD>
+DEVINL void at_tile_load(ushort8 (&r)[HD / 64], const unsigned short* __restrict__ base, long long rstride,
+                         int row0, int last, int tid) {
+#pragma unroll
+  for (int i = 0; i < HD / 64; ++i) {
+    const int e = tid + i * 256;
+    r[i] = *(const ushort8*)(base + (size_t)min(row0 + e / (HD / 8), last) * rstride + (e % (HD / 8)) * 8);
+  }
+}
+
+// B operand of a contraction over the 32 rows of a staged tile, 16 dims at
+// `tile` (its row 0, first dim of the group), by the transposing read. In a
+// 16-lane group, lane L points at 4 dims of row L >> 2 and lane i receives dim
+// i of those 4 rows; quad qd takes rows 4 qd .. and 16 + 4 qd .., the order in
+// which at_image_frag reads the other operand.
+DEVINL bf16x8 at_tr_frag(const unsigned short* tile, int row_stride, int lane) {
+  const unsigned short* p = tile + ((lane >> 4) * 4 + ((lane & 15) >> 2)) * row_stride + (lane & 3) * 4;
+  const v4i16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)p);
+  const v4i16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(p + 16 * row_stride));
+  return __builtin_bit_cast(bf16x8, (v8i16)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// A operand from a 16 x 32 image (48-element rows), columns in at_tr_frag's order
+DEVINL bf16x8 at_image_frag(const unsigned short* img, int lane) {
+  const unsigned short* p = img + (lane & 15) * 48 + (lane >> 4) * 4;
+  const bf16x4 lo = *reinterpret_cast<const bf16x4*>(p);
+  const bf16x4 hi = *reinterpret_cast<const bf16x4*>(p + 16);
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// Forward. Grid: one 4-wave workgroup per (q block, b, h), heads fastest (the
+// G heads of a kv head are adjacent: their K/V tiles hit in L2) and late q
+// blocks first. Rows at or beyond S are clamped on load and never stored.
+template <int HD, int NT>
+__global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_train_fwd_kernel(
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
+    const unsigned short* __restrict__ v, unsigned short* __restrict__ out, float* __restrict__ lse,
+    int B, int S, int H, int KVH, AtStrides qs, AtStrides ks, AtStrides vs, float scale) {
+  constexpr int NC = HD / 32, NG = HD / 16, PC = HD / 64;
+  constexpr int QROWS = 64 * NT;
+  constexpr int KROW = AT_BROW(HD), VROW = AT_TROW(HD);
+  const int qblocks = (S + QROWS - 1) / QROWS;
+  const int h = blockIdx.x % H;
+  const int t1 = blockIdx.x / H;
+  const int b = t1 % B;
+  const int qb = qblocks - 1 - t1 / B;
+  const int kvh = h / (H / KVH);
+  const int tid = threadIdx.x;
+  const int wv = tid >> 6;
+  const int lane = tid & 63;
+  const int col = lane & 15, quad = lane >> 4;
+
+  __shared__ __attribute__((aligned(16))) unsigned short kv_lds[2][32 * KROW + 32 * VROW];
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][16 * 48 * NT];
+
+  const int r0 = qb * QROWS + wv * (16 * NT);
+  bf16x8 qf[NT][NC];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int row = min(r0 + t * 16 + col, S - 1);
+    const unsigned short* qrow = q + (size_t)b * qs.b + (size_t)row * qs.s + (size_t)h * qs.h;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) qf[t][c] = frag_load<false>(qrow + c * 32 + quad * 8);
+  }
+
+  float m[NT][4], lsum[NT][4];
+  floatx4 acco[NT][NG];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[t][r] = -INFINITY; lsum[t][r] = 0.f; }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int g = 0; g < NG; ++g) acco[t][g] = (floatx4)(0.f);
+
+  // causal end of the block: positions [0, kv_end), kv_end <= S
+  const int kv_end = min(qb * QROWS + QROWS, S);
+  const int ntiles = (kv_end + 31) >> 5;
+
+  const unsigned short* kb = k + (size_t)b * ks.b + (size_t)kvh * ks.h;
+  const unsigned short* vb = v + (size_t)b * vs.b + (size_t)kvh * vs.h;
+  ushort8 sk[PC], sv[PC];
+  auto stage_load = [&](int tp) __attribute__((always_inline)) {
+    at_tile_load<HD>(sk, kb, ks.s, tp * 32, S - 1, tid);  // clamped positions are >= kv_end: masked
+    at_tile_load<HD>(sv, vb, vs.s, tp * 32, S - 1, tid);
+  };
+  auto stage_store = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < PC; ++i) {
+      const int e = tid + i * 256;
+      *(ushort8*)(kv_lds[buf] + (e / (HD / 8)) * KROW + (e % (HD / 8)) * 8) = sk[i];
+      *(ushort8*)(kv_lds[buf] + 32 * KROW + (e / (HD / 8)) * VROW + (e % (HD / 8)) * 8) = sv[i];
+    }
+  };
+
+  stage_load(0);
+  stage_store(0);
+  mla_pf_barrier();
+
+  unsigned short* plds = plds_all[wv];
+  for (int tp = 0; tp < ntiles; ++tp) {
+    const int buf = tp & 1;
+    const bool more = tp + 1 < ntiles;
+    if (more) stage_load(tp + 1);  // in flight under this tile's MFMAs
+    const unsigned short* dk = kv_lds[buf];
+    const unsigned short* dv = kv_lds[buf] + 32 * KROW;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      // wave-uniform: a tile wholly above the sub-tile's last row is all masked.
+      // Tile 0 is never skipped and every row sees position 0, so m is finite
+      // from the first tile on.
+      if (tp * 32 > r0 + t * 16 + 15) continue;
+      floatx4 sc[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        sc[hh] = (floatx4)(0.f);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const bf16x8 kf = *reinterpret_cast<const bf16x8*>(dk + (hh * 16 + col) * KROW + c * 32 + quad * 8);
+          sc[hh] = Frag<false>::mfma(qf[t][c], kf, sc[hh]);
+        }
+      }
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int pos = tp * 32 + hh * 16 + col;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = r0 + t * 16 + quad * 4 + r;
+          sc[hh][r] = (pos <= row) ? sc[hh][r] * scale : -INFINITY;
+        }
+      }
+      float rmax[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(sc[0][r], sc[1][r]);
+#pragma unroll
+      for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(rmax[r], mla_pf_lane_xor(rmax[r], lane, mm));
+      float alpha[4], rsum[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float mn = fmaxf(m[t][r], rmax[r]);
+        alpha[r] = (lsum[t][r] > 0.f) ? __expf(m[t][r] - mn) : 0.f;
+        m[t][r] = mn;
+        const float p0 = __expf(sc[0][r] - mn);
+        const float p1 = __expf(sc[1][r] - mn);
+        sc[0][r] = p0;
+        sc[1][r] = p1;
+        rsum[r] = p0 + p1;
+      }
+#pragma unroll
+      for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rsum[r] += mla_pf_lane_xor(rsum[r], lane, mm);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) lsum[t][r] = lsum[t][r] * alpha[r] + rsum[r];
+      attn_rescale(acco[t], alpha, 1.f);
+      unsigned short* pl = plds + t * 16 * 48;
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          pl[(quad * 4 + r) * 48 + hh * 16 + col] = f2b(sc[hh][r]);
+      const bf16x8 pf = at_image_frag(pl, lane);
+#pragma unroll
+      for (int g = 0; g < NG; ++g)
+        acco[t][g] = Frag<false>::mfma(pf, at_tr_frag(dv + g * 16, VROW, lane), acco[t][g]);
+    }
+    if (more) stage_store(buf ^ 1);  // last read before the previous barrier
+    mla_pf_barrier();
+  }
+
+  // out[b, row, h, :] = acc / l (contiguous), lse[b, h, row] = m + log(l)
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = r0 + t * 16 + quad * 4 + r;
+      if (row < S) {
+        const float inv = 1.f / lsum[t][r];
+        unsigned short* orow = out + (((size_t)b * S + row) * H + h) * HD;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) orow[g * 16 + col] = f2b(acco[t][g][r] * inv);
+        if (col == 0) lse[((size_t)b * H + h) * S + row] = m[t][r] + __logf(lsum[t][r]);
+      }
+    }
+  }
+}
+
+// Backward, dQ. The forward's split and grid; a wave holds its rows' Q and dO
+// fragments, their lse and delta[r] = sum_d dO[r, d] out[r, d] (fp32, computed
+// here from the wave's own rows and written to delta [B, H, S] for the dkv
+// kernel). Per tile P = exp(scale S - lse), dS = P (dP - delta), dQ += dS K;
+// writes scale * dQ. dout / out / dq are contiguous [B, S, H, HD].
+template <int HD, int NT>
+__global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_train_bwd_dq_kernel(
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
+    const unsigned short* __restrict__ v, const unsigned short* __restrict__ out,
+    const unsigned short* __restrict__ dout, const float* __restrict__ lse, float* __restrict__ delta,
+    unsigned short* __restrict__ dq, int B, int S, int H, int KVH,
+    AtStrides qs, AtStrides ks, AtStrides vs, float scale) {
+  constexpr int NC = HD / 32, NG = HD / 16, PC = HD / 64;
+  constexpr int QROWS = 64 * NT;
+  constexpr int KROW = AT_TROW(HD), VROW = AT_BROW(HD);
+  const int qblocks = (S + QROWS - 1) / QROWS;
+  const int h = blockIdx.x % H;
+  const int t1 = blockIdx.x / H;
+  const int b = t1 % B;
+  const int qb = qblocks - 1 - t1 / B;
+  const int kvh = h / (H / KVH);
+  const int tid = threadIdx.x;
+  const int wv = tid >> 6;
+  const int lane = tid & 63;
+  const int col = lane & 15, quad = lane >> 4;
+
+  __shared__ __attribute__((aligned(16))) unsigned short kv_lds[2][32 * KROW + 32 * VROW];
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][16 * 48 * NT];
+
+  const int r0 = qb * QROWS + wv * (16 * NT);
+  const size_t bh = (size_t)b * H + h;
+  bf16x8 qf[NT][NC], dof[NT][NC];
+  float ls[NT][4], dl[NT][4];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int row = min(r0 + t * 16 + col, S - 1);
+    const unsigned short* qrow = q + (size_t)b * qs.b + (size_t)row * qs.s + (size_t)h * qs.h;
+    const size_t orow = (((size_t)b * S + row) * H + h) * HD;
+    float d = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      qf[t][c] = frag_load<false>(qrow + c * 32 + quad * 8);
+      dof[t][c] = frag_load<false>(dout + orow + c * 32 + quad * 8);
+      const bf16x8 of = frag_load<false>(out + orow + c * 32 + quad * 8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) d += (float)dof[t][c][j] * (float)of[j];
+    }
+    d += mla_pf_lane_xor(d, lane, 16);
+    d += mla_pf_lane_xor(d, lane, 32);  // every lane: delta of row `col`
+    if (quad == 0 && r0 + t * 16 + col < S) delta[bh * S + row] = d;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      dl[t][r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((quad * 4 + r) << 2, __builtin_bit_cast(int, d)));
+      ls[t][r] = lse[bh * S + min(r0 + t * 16 + quad * 4 + r, S - 1)];
+    }
+  }
+
+  floatx4 acc[NT][NG];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int g = 0; g < NG; ++g) acc[t][g] = (floatx4)(0.f);
+
+  const int kv_end = min(qb * QROWS + QROWS, S);
+  const int ntiles = (kv_end + 31) >> 5;
+  const unsigned short* kb = k + (size_t)b * ks.b + (size_t)kvh * ks.h;
+  const unsigned short* vb = v + (size_t)b * vs.b + (size_t)kvh * vs.h;
+  ushort8 sk[PC], sv[PC];
+  auto stage_load = [&](int tp) __attribute__((always_inline)) {
+    at_tile_load<HD>(sk, kb, ks.s, tp * 32, S - 1, tid);
+    at_tile_load<HD>(sv, vb, vs.s, tp * 32, S - 1, tid);
+  };
+  auto stage_store = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < PC; ++i) {
+      const int e = tid + i * 256;
+      *(ushort8*)(kv_lds[buf] + (e / (HD / 8)) * KROW + (e % (HD / 8)) * 8) = sk[i];
+      *(ushort8*)(kv_lds[buf] + 32 * KROW + (e / (HD / 8)) * VROW + (e % (HD / 8)) * 8) = sv[i];
+    }
+  };
+
+  stage_load(0);
+  stage_store(0);
+  mla_pf_barrier();
+
+  unsigned short* plds = plds_all[wv];
+  for (int tp = 0; tp < ntiles; ++tp) {
+    const int buf = tp & 1;
+    const bool more = tp + 1 < ntiles;
+    if (more) stage_load(tp + 1);
+    const unsigned short* dk = kv_lds[buf];
+    const unsigned short* dv = kv_lds[buf] + 32 * KROW;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      if (tp * 32 > r0 + t * 16 + 15) continue;  // wave-uniform: all masked, dS = 0
+      floatx4 sc[2], dp[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        sc[hh] = (floatx4)(0.f);
+        dp[hh] = (floatx4)(0.f);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const bf16x8 kf = *reinterpret_cast<const bf16x8*>(dk + (hh * 16 + col) * KROW + c * 32 + quad * 8);
+          const bf16x8 vf = *reinterpret_cast<const bf16x8*>(dv + (hh * 16 + col) * VROW + c * 32 + quad * 8);
+          sc[hh] = Frag<false>::mfma(qf[t][c], kf, sc[hh]);
+          dp[hh] = Frag<false>::mfma(dof[t][c], vf, dp[hh]);
+        }
+      }
+      unsigned short* pl = plds + t * 16 * 48;
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int pos = tp * 32 + hh * 16 + col;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = r0 + t * 16 + quad * 4 + r;
+          const float p = (pos <= row) ? __expf(sc[hh][r] * scale - ls[t][r]) : 0.f;
+          pl[(quad * 4 + r) * 48 + hh * 16 + col] = f2b(p * (dp[hh][r] - dl[t][r]));
+        }
+      }
+      const bf16x8 dsf = at_image_frag(pl, lane);
+#pragma unroll
+      for (int g = 0; g < NG; ++g)
+        acc[t][g] = Frag<false>::mfma(dsf, at_tr_frag(dk + g * 16, KROW, lane), acc[t][g]);
+    }
+    if (more) stage_store(buf ^ 1);
+    mla_pf_barrier();
+  }
+
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = r0 + t * 16 + quad * 4 + r;
+      if (row < S) {
+        unsigned short* drow = dq + (((size_t)b * S + row) * H + h) * HD;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) drow[g * 16 + col] = f2b(acc[t][g][r] * scale);
+      }
+    }
+  }
+}
+
+// Backward, dK and dV. Grid: one 4-wave workgroup per (kv block of 64
+// positions, b, kv head), early kv blocks (the long ones) first; a wave owns
+// 16 positions, their K and V fragments in registers and the fp32 dK / dV
+// accumulators, 2 * HD / 4 registers per lane. It walks the G query heads of
+// the kv head and, inside, the 32-row q tiles from the block's first position
+// to S (one flat, double-buffered loop); a tile's Q and dO rows, lse and delta
+// are staged through LDS. Per tile, with i = position, j = q row:
+//   S^T = K Q^T, P^T = exp(scale S^T - lse[j]) where j >= i and j < S, else 0
+//   dV += P^T dO;  dP^T = V dO^T;  dS^T = P^T (dP^T - delta[j]);  dK += dS^T Q
+// All heads and rows are summed in registers in that fixed order and each
+// dK / dV row is written once: no atomics, deterministic.
+template <int HD>
+__global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_train_bwd_dkv_kernel(
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
+    const unsigned short* __restrict__ v, const unsigned short* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    unsigned short* __restrict__ dk, unsigned short* __restrict__ dv, int B, int S, int H, int KVH,
+    AtStrides qs, AtStrides ks, AtStrides vs, float scale) {
+  constexpr int NC = HD / 32, NG = HD / 16, PC = HD / 64;
+  constexpr int ROW = AT_TROW(HD);
+  const int kvh = blockIdx.x % KVH;
+  const int t1 = blockIdx.x / KVH;
+  const int b = t1 % B;
+  const int kb = t1 / B;
+  const int G = H / KVH;
+  const int tid = threadIdx.x;
+  const int wv = tid >> 6;
+  const int lane = tid & 63;
+  const int col = lane & 15, quad = lane >> 4;
+
+  __shared__ __attribute__((aligned(16))) unsigned short qd_lds[2][2 * 32 * ROW];  // Q tile, dO tile
+  __shared__ float ld_lds[2][64];                                                  // lse[32], delta[32]
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][2 * 16 * 48]; // P^T image, dS^T image
+
+  const int p0 = kb * 64 + wv * 16;
+  bf16x8 kf[NC], vf[NC];
+  {
+    const int pos = min(p0 + col, S - 1);  // positions >= S: every q row is masked for them, never stored
+    const unsigned short* krow = k + (size_t)b * ks.b + (size_t)pos * ks.s + (size_t)kvh * ks.h;
+    const unsigned short* vrow = v + (size_t)b * vs.b + (size_t)pos * vs.s + (size_t)kvh * vs.h;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      kf[c] = frag_load<false>(krow + c * 32 + quad * 8);
+      vf[c] = frag_load<false>(vrow + c * 32 + quad * 8);
+    }
+  }
+  floatx4 acck[NG], accv[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) { acck[g] = (floatx4)(0.f); accv[g] = (floatx4)(0.f); }
+
+  const int tq0 = kb * 2;                    // the q tile holding the block's first position
+  const int ntq = ((S + 31) >> 5) - tq0;     // >= 1: kb * 64 < S
+  const int total = G * ntq;
+  ushort8 sq[PC], sdo[PC];
+  float sld;
+  auto stage_load = [&](int it) __attribute__((always_inline)) {
+    const int h = kvh * G + it / ntq;
+    const int row0 = (tq0 + it % ntq) * 32;
+    at_tile_load<HD>(sq, q + (size_t)b * qs.b + (size_t)h * qs.h, qs.s, row0, S - 1, tid);
+    at_tile_load<HD>(sdo, dout + ((size_t)b * S * H + h) * HD, (long long)H * HD, row0, S - 1, tid);
+    if (tid < 64) sld = (tid < 32 ? lse : delta)[((size_t)b * H + h) * S + min(row0 + (tid & 31), S - 1)];
+  };
+  auto stage_store = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < PC; ++i) {
+      const int e = tid + i * 256;
+      *(ushort8*)(qd_lds[buf] + (e / (HD / 8)) * ROW + (e % (HD / 8)) * 8) = sq[i];
+      *(ushort8*)(qd_lds[buf] + 32 * ROW + (e / (HD / 8)) * ROW + (e % (HD / 8)) * 8) = sdo[i];
+    }
+    if (tid < 64) ld_lds[buf][tid] = sld;
+  };
+
+  stage_load(0);
+  stage_store(0);
+  mla_pf_barrier();
+
+  unsigned short* pl = plds_all[wv];
+  unsigned short* dsl = plds_all[wv] + 16 * 48;
+  for (int it = 0; it < total; ++it) {
+    const int buf = it & 1;
+    const bool more = it + 1 < total;
+    if (more) stage_load(it + 1);
+    const unsigned short* tq = qd_lds[buf];
+    const unsigned short* tdo = qd_lds[buf] + 32 * ROW;
+    const int row0 = (tq0 + it % ntq) * 32;
+    if (row0 + 31 >= p0) {  // wave-uniform: a tile wholly before the wave's positions is all masked
+      floatx4 sc[2], dp[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        sc[hh] = (floatx4)(0.f);
+        dp[hh] = (floatx4)(0.f);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const bf16x8 qb = *reinterpret_cast<const bf16x8*>(tq + (hh * 16 + col) * ROW + c * 32 + quad * 8);
+          const bf16x8 ob = *reinterpret_cast<const bf16x8*>(tdo + (hh * 16 + col) * ROW + c * 32 + quad * 8);
+          sc[hh] = Frag<false>::mfma(kf[c], qb, sc[hh]);
+          dp[hh] = Frag<false>::mfma(vf[c], ob, dp[hh]);
+        }
+      }
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int qrow = row0 + hh * 16 + col;
+        const float l = ld_lds[buf][hh * 16 + col];
+        const float de = ld_lds[buf][32 + hh * 16 + col];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int pos = p0 + quad * 4 + r;
+          const float p = (qrow >= pos && qrow < S) ? __expf(sc[hh][r] * scale - l) : 0.f;
+          pl[(quad * 4 + r) * 48 + hh * 16 + col] = f2b(p);
+          dsl[(quad * 4 + r) * 48 + hh * 16 + col] = f2b(p * (dp[hh][r] - de));
+        }
+      }
+      const bf16x8 pf = at_image_frag(pl, lane);
+      const bf16x8 dsf = at_image_frag(dsl, lane);
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        accv[g] = Frag<false>::mfma(pf, at_tr_frag(tdo + g * 16, ROW, lane), accv[g]);
+        acck[g] = Frag<false>::mfma(dsf, at_tr_frag(tq + g * 16, ROW, lane), acck[g]);
+      }
+    }
+    if (more) stage_store(buf ^ 1);
+    mla_pf_barrier();
+  }
+
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int pos = p0 + quad * 4 + r;
+    if (pos < S) {
+      const size_t o = (((size_t)b * S + pos) * KVH + kvh) * HD;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        dk[o + g * 16 + col] = f2b(acck[g][r] * scale);
+        dv[o + g * 16 + col] = f2b(accv[g][r]);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // fp8-KV flash prefill (HD = 128 or 256, causal, GQA): attn_prefill_mfma_kernel
 // over the e4m3 packed cache and its per-position scales sk / sv [B, KVH, T32].
 //
@@ -5046,6 +5558,86 @@ torch::Tensor attn_prefill_mla(torch::Tensor q, torch::Tensor kvx, torch::Tensor
   return out;
 }
 
+// Training attention. q: [B, S, H, hd], k / v: [B, S, KVH, hd] bf16, hd 64 or
+// 128, read in place: any b / s / head strides in whole 16-byte pieces, last
+// dim contiguous (views of the packed qkv GEMM output, no copy).
+struct AttnTrainShape {
+  int B, S, H, KVH, hd;
+  AtStrides qs, ks, vs;
+};
+
+static AttnTrainShape attn_train_shape(const char* what, const torch::Tensor& q, const torch::Tensor& k,
+                                       const torch::Tensor& v, double scale) {
+  for (const torch::Tensor* t : {&q, &k, &v}) {
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kBFloat16 && t->dim() == 4, what, ": q, k, v are 4-d bf16 GPU tensors");
+    TORCH_CHECK(t->stride(3) == 1 && (uintptr_t)t->data_ptr() % 16 == 0, what, ": rows must be contiguous and 16-byte aligned");
+    for (int d = 0; d < 3; ++d) TORCH_CHECK(t->stride(d) % 8 == 0, what, ": strides in whole 16-byte pieces");
+  }
+  AttnTrainShape s{(int)q.size(0), (int)q.size(1), (int)q.size(2), (int)k.size(2), (int)q.size(3),
+                   {q.stride(0), q.stride(1), q.stride(2)}, {k.stride(0), k.stride(1), k.stride(2)},
+                   {v.stride(0), v.stride(1), v.stride(2)}};
+  TORCH_CHECK(s.hd == 64 || s.hd == 128, what, ": head dim 64 or 128 only, got ", s.hd);
+  CHK(s.B > 0 && s.S > 0 && s.H > 0 && s.KVH > 0 && s.H % s.KVH == 0 && scale > 0.0);
+  CHK(k.size(0) == s.B && k.size(1) == s.S && k.size(3) == s.hd && v.sizes() == k.sizes());
+  CHK((int64_t)s.B * s.H * ((s.S + 63) / 64) <= INT_MAX);
+  return s;
+}
+
+template <class F>
+static void dispatch_train_hd(int hd, F&& f) {
+  if (hd == 64) f(IntC<64>{});
+  else f(IntC<128>{});
+}
+
+// -> (out [B, S, H, hd] bf16, lse [B, H, S] fp32 in units of the scaled score)
+std::vector<torch::Tensor> attn_train_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, double scale) {
+  const AttnTrainShape s = attn_train_shape("attn_train_fwd", q, k, v, scale);
+  auto out = torch::empty({s.B, s.S, s.H, s.hd}, q.options());
+  auto lse = torch::empty({s.B, s.H, s.S}, q.options().dtype(torch::kFloat32));
+  dispatch_train_hd(s.hd, [&](auto hd) {
+    constexpr int HD = decltype(hd)::value, NT = ATTN_TRAIN_NT(HD);
+    const unsigned blocks = (unsigned)s.B * ((s.S + 64 * NT - 1) / (64 * NT)) * s.H;
+    hipLaunchKernelGGL((attn_train_fwd_kernel<HD, NT>), dim3(blocks), dim3(256), 0, cur_stream(),
+                       (const unsigned short*)q.data_ptr(), (const unsigned short*)k.data_ptr(),
+                       (const unsigned short*)v.data_ptr(), (unsigned short*)out.data_ptr(),
+                       lse.data_ptr<float>(), s.B, s.S, s.H, s.KVH, s.qs, s.ks, s.vs, (float)scale);
+  });
+  return {out, lse};
+}
+
+// dout / out: [B, S, H, hd] bf16 contiguous, lse: what attn_train_fwd returned
+// -> (dq [B, S, H, hd], dk, dv [B, S, KVH, hd]) bf16 contiguous. Two launches on
+// the current stream; the workspace is delta [B, H, S] fp32.
+std::vector<torch::Tensor> attn_train_bwd(torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                                          torch::Tensor out, torch::Tensor lse, double scale) {
+  const AttnTrainShape s = attn_train_shape("attn_train_bwd", q, k, v, scale);
+  for (const torch::Tensor* t : {&dout, &out})
+    CHK(t->is_cuda() && t->dtype() == torch::kBFloat16 && t->is_contiguous() && t->sizes() == q.sizes() &&
+        (uintptr_t)t->data_ptr() % 16 == 0);
+  CHK(lse.is_cuda() && lse.dtype() == torch::kFloat32 && lse.is_contiguous());
+  CHK(lse.dim() == 3 && lse.size(0) == s.B && lse.size(1) == s.H && lse.size(2) == s.S);
+  auto delta = torch::empty_like(lse);
+  auto dq = torch::empty({s.B, s.S, s.H, s.hd}, q.options());
+  auto dk = torch::empty({s.B, s.S, s.KVH, s.hd}, q.options());
+  auto dv = torch::empty({s.B, s.S, s.KVH, s.hd}, q.options());
+  dispatch_train_hd(s.hd, [&](auto hd) {
+    constexpr int HD = decltype(hd)::value, NT = ATTN_TRAIN_NT(HD);
+    const unsigned qblocks = (unsigned)s.B * ((s.S + 64 * NT - 1) / (64 * NT)) * s.H;
+    hipLaunchKernelGGL((attn_train_bwd_dq_kernel<HD, NT>), dim3(qblocks), dim3(256), 0, cur_stream(),
+                       (const unsigned short*)q.data_ptr(), (const unsigned short*)k.data_ptr(),
+                       (const unsigned short*)v.data_ptr(), (const unsigned short*)out.data_ptr(),
+                       (const unsigned short*)dout.data_ptr(), lse.data_ptr<float>(), delta.data_ptr<float>(),
+                       (unsigned short*)dq.data_ptr(), s.B, s.S, s.H, s.KVH, s.qs, s.ks, s.vs, (float)scale);
+    const unsigned kvblocks = (unsigned)s.B * ((s.S + 63) / 64) * s.KVH;
+    hipLaunchKernelGGL((attn_train_bwd_dkv_kernel<HD>), dim3(kvblocks), dim3(256), 0, cur_stream(),
+                       (const unsigned short*)q.data_ptr(), (const unsigned short*)k.data_ptr(),
+                       (const unsigned short*)v.data_ptr(), (const unsigned short*)dout.data_ptr(),
+                       lse.data_ptr<float>(), delta.data_ptr<float>(), (unsigned short*)dk.data_ptr(),
+                       (unsigned short*)dv.data_ptr(), s.B, s.S, s.H, s.KVH, s.qs, s.ks, s.vs, (float)scale);
+  });
+  return {dq, dk, dv};
+}
+
 torch::Tensor mfma16_probe(torch::Tensor a, torch::Tensor b) {
   CHK(a.is_cuda() && a.dtype() == torch::kBFloat16 && a.is_contiguous() && a.numel() == 16 * 32);
   CHK(b.is_cuda() && b.dtype() == torch::kBFloat16 && b.is_contiguous() && b.numel() == 32 * 16);
@@ -5650,6 +6242,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MLA decode attention (absorbed latent MQA) on matrix cores; fp8 cache mode",
         py::arg("q"), py::arg("kp"), py::arg("vp"), py::arg("seq_lens"),
         py::arg("scale") = 0.0, py::arg("q_scale") = py::none(), py::arg("k_scale") = py::none());
+  m.def("attn_train_fwd", &attn_train_fwd,
+        "training attention forward (causal GQA, bf16, hd 64 or 128; q / k / v strided views) -> (out, lse [B, H, S])",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"));
+  m.def("attn_train_bwd", &attn_train_bwd,
+        "training attention backward, deterministic -> (dq, dk, dv) bf16 contiguous",
+        py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("scale"));
   m.def("attn_prefill_mla", &attn_prefill_mla,
         "MLA causal flash prefill (qk 192 = nope 128 | shared rope 64, v 128) on matrix cores, "
         "K/V read in place from the kv_b_proj output and the plain rope cache",

@@ -192,6 +192,20 @@ def attn_prefill(
   return out.transpose(1, 2).to(q.dtype)
 
 
+def attn_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
+  """Cache-free causal GQA attention, differentiable (training / eval):
+  q [B, S, H, hd], k / v [B, S, KVH, hd] -> [B, S, H, hd]. fp32 sdpa over K / V
+  expanded per query head: the expression of the llama-family training forward."""
+  rep = q.shape[2] // k.shape[2]
+  out = F.scaled_dot_product_attention(
+    q.transpose(1, 2).float(),
+    k.transpose(1, 2).repeat_interleave(rep, dim=1).float(),
+    v.transpose(1, 2).repeat_interleave(rep, dim=1).float(),
+    is_causal=True, scale=scale,
+  ).to(q.dtype)
+  return out.transpose(1, 2)
+
+
 def attn_decode(
   q: torch.Tensor,
   k_cache: torch.Tensor,
