@@ -18,6 +18,10 @@ needs the 8-GPU ring). YaRN long-context rope scaling is implemented
 (NTK-by-parts frequency blend + mscale corrections, validated against
 transformers).
 
+Training: forward(caches=None) is the cache-free forward (same modules and
+weights; MLAttention._forward_nocache), whose attention is
+ops.attn_train_mla's flash forward / backward kernels under XOT_TRAIN_ATTN=1.
+
 Cache contract: caches[idx] is a LayerKV whose k tensor stores the kv_nope
 latent [B, 1, T, kv_lora_rank] and v tensor stores the roped shared key
 [B, 1, T, qk_rope_head_dim] (see ModelConfig.kv_cache_dims()).
@@ -96,8 +100,39 @@ class MLAttention(nn.Module):
       m = 0.1 * rs.mscale_all_dim * math.log(rs.factor) + 1.0
       self.scale *= m * m
 
+  def _forward_nocache(self, x, cos, sin, positions):
+    """Cache-free causal MLA attention (training / eval): the projections and
+    the _rms / _rope calls of forward's eager branch, no cache tensors, the
+    same self.scale (YaRN correction included). kvx is the kv_b_proj output
+    viewed per head and the roped shared key stays one row per position: the
+    attention op takes both as they are. Under XOT_TRAIN_ATTN=1, in bf16 on the
+    GPU at dims ops.attn_train_mla_fits, that op is the attn_train_mla flash
+    forward / backward kernels; otherwise the explicit fp32 expression."""
+    cfg = self.cfg
+    B, S, _ = x.shape
+    H = cfg.n_heads
+    nope, rope_d, vd = cfg.qk_nope_head_dim, cfg.qk_rope_head_dim, cfg.v_head_dim
+    if cfg.q_lora_rank:
+      q = self.q_b_proj(_rms(self.q_a_proj(x), self.q_a_layernorm, cfg.norm_eps))
+    else:
+      q = self.q_proj(x)
+    q = q.view(B, S, H, self.qk_head_dim)
+    ckv = self.kv_a_proj_with_mqa(x)
+    cs, sn = _rope_rows(cos, sin, positions, B, S)
+    q = torch.cat([q[..., :nope], _rope(q[..., nope:], cs, sn, cfg.rope_interleave)], dim=-1)
+    kv_nope = _rms(ckv[..., : cfg.kv_lora_rank], self.kv_a_layernorm, cfg.norm_eps)
+    k_rot = _rope(ckv[..., cfg.kv_lora_rank:].view(B, S, 1, rope_d), cs, sn, cfg.rope_interleave)[:, :, 0, :]
+    kvx = self.kv_b_proj(kv_nope).view(B, S, H, nope + vd)
+    if ops.attn_train_enabled() and x.is_cuda and x.dtype == torch.bfloat16 and ops.attn_train_mla_fits(nope, rope_d, vd):
+      out = ops.attn_train_mla(q, kvx, k_rot, self.scale)  # XOT_TRAIN_ATTN=1: kvx and k_rot read in place
+    else:
+      out = ops.torch_ref.attn_train_mla(q, kvx, k_rot, self.scale)
+    return self.o_proj(out.reshape(B, S, H * vd))
+
   def forward(self, x, cos, sin, positions, kv, start_pos: int,
               is_decode: bool = False, seq_lens=None):
+    if kv is None:
+      return self._forward_nocache(x, cos, sin, positions)
     cfg = self.cfg
     B, S, _ = x.shape
     H = cfg.n_heads
@@ -412,12 +447,11 @@ class DeepseekV3Model(ShardBase):
   def forward(self, x, caches, positions, start_pos: int, is_decode: bool = False,
               seq_lens=None, last_only: bool = True):
     cfg = self.cfg
-    if caches is None:
-      raise NotImplementedError("MLA training forward is not implemented (inference only)")
     h = self.embed_tokens(x) if x.dtype in (torch.int32, torch.int64) else x
-    caches, positions, use_ckpt = self._enter(caches, positions)  # use_ckpt: never, caches are given
+    caches, positions, use_ckpt = self._enter(caches, positions)  # caches None: the cache-free training forward
     for idx, lid in enumerate(self.local_layer_ids):
-      h = self._run_layer(self.layers[str(lid)], use_ckpt, h, positions, caches[idx],
+      kv = caches[idx] if caches is not None else None
+      h = self._run_layer(self.layers[str(lid)], use_ckpt, h, positions, kv,
                           start_pos, is_decode, seq_lens)
     if not self.shard.is_last_layer:
       return h

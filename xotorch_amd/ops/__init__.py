@@ -231,7 +231,8 @@ def attn_prefill(q, k_cache, v_cache, start_pos: int, s_len: int, kp=None, vp=No
 def attn_train_enabled() -> bool:
   """XOT_TRAIN_ATTN (default 0, read per call): the llama-family training
   forward runs attention on attn_train's flash forward / backward kernels
-  instead of fp32 sdpa over K / V expanded per query head."""
+  instead of fp32 sdpa over K / V expanded per query head, and the DeepSeek
+  one on attn_train_mla's instead of the explicit fp32 expression."""
   return os.getenv("XOT_TRAIN_ATTN", "0") == "1"
 
 
@@ -269,6 +270,44 @@ def attn_train(q, k, v, scale=None):
      and attn_train_fits(q.shape[2], k.shape[2], q.shape[3]):
     return _AttnTrain.apply(q, k, v, float(scale) if scale is not None else q.shape[3] ** -0.5)
   return torch_ref.attn_train(q, k, v, scale)
+
+
+def attn_train_mla_fits(nope: int, rope: int, vd: int) -> bool:
+  """Whether the MLA training attention kernels take these head dims."""
+  return (nope, rope, vd) == (128, 64, 128)
+
+
+class _AttnTrainMla(torch.autograd.Function):
+  """attn_train_mla_fwd / attn_train_mla_bwd under autograd, with plain
+  save_for_backward like _AttnTrain."""
+
+  @staticmethod
+  def forward(ctx, q, kvx, k_rot, scale):
+    out, lse = _gpu().attn_train_mla_fwd(q, kvx, k_rot, scale)
+    ctx.save_for_backward(q, kvx, k_rot, out, lse)
+    ctx.scale = scale
+    return out
+
+  @staticmethod
+  def backward(ctx, dout):
+    q, kvx, k_rot, out, lse = ctx.saved_tensors
+    dq, d_kvx, d_k_rot = _gpu().attn_train_mla_bwd(dout.contiguous(), q, kvx, k_rot, out, lse, ctx.scale)
+    return dq, d_kvx, d_k_rot, None
+
+
+def attn_train_mla(q, kvx, k_rot, scale):
+  """Cache-free causal MLA attention, differentiable: q [B, S, H, nope + rope]
+  (nope | roped tail), kvx [B, S, H, nope + vd] (the kv_b_proj output per head,
+  k_nope | v), k_rot [B, S, rope] (the roped key all heads share) ->
+  [B, S, H, vd]. bf16 GPU tensors at dims that attn_train_mla_fits run the
+  flash forward and the deterministic backward kernels, which read all three
+  in place (any strides, contiguous rows) and return the gradient of kvx as
+  one tensor and that of k_rot summed over the heads. Everything else is
+  torch_ref.attn_train_mla."""
+  if q.is_cuda and q.dtype == kvx.dtype == k_rot.dtype == torch.bfloat16 \
+     and attn_train_mla_fits(q.shape[3] - k_rot.shape[2], k_rot.shape[2], kvx.shape[3] - q.shape[3] + k_rot.shape[2]):
+    return _AttnTrainMla.apply(q, kvx, k_rot, float(scale))
+  return torch_ref.attn_train_mla(q, kvx, k_rot, scale)
 
 
 def attn_decode(q, k_cache, v_cache, seq_len, kp=None, vp=None,

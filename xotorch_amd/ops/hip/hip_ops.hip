@@ -2869,6 +2869,522 @@ __global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_train_bwd_dkv_ke
 }
 
 // ---------------------------------------------------------------------------
+// MLA training attention (causal, non-absorbed, bf16): nope 128 | rope 64 keys,
+// 128-dim values. The operands are the training forward's own tensors, read in
+// place through their strides:
+//   q    [B, S, H, 192]  nope | roped tail
+//   kvx  [B, S, H, 256]  the kv_b_proj output per head: k_nope | v
+//   rot  [B, S, 64]      the ONE roped key row per position, all heads
+// No [B, S, H, 192] key is built and nothing is [S, S]. The forward is
+// attn_prefill_mla_kernel's data flow at start_pos 0 plus the lse store; the
+// backward is attn_train_bwd_*'s with three differences. The score contraction
+// is 192 wide and the dP contraction 128, so K-side tiles and V-side tiles have
+// different widths and strides. K and V of a head leave as ONE tensor
+// d_kvx [B, S, H, 256] = dK_nope | dV, the layout kv_b_proj's backward GEMM
+// reads. And the key's rope part belongs to all H heads: each (block, b, h)
+// writes its dK_rope rows in fp32 to a workspace [B, H, S, 64], once, and
+// attn_train_mla_rope_reduce_kernel adds the heads in ascending order and
+// rounds once to bf16: no atomics, two runs give the same bits.
+// LDS row strides, by the bank rule in docs/KERNELS.md (4 x odd dwords for
+// b128-only tiles, 8 x odd for tiles the transposing read also takes):
+//   192-wide, b128 only (forward K)                200 el = 100 dw = 4 x 25
+//   192-wide, both ways (dq K, dkv Q)              208 el = 104 dw = 8 x 13
+//   128-wide, b128 only (dq V)                     136 el =  68 dw = 4 x 17
+//   128-wide, transposing or both (fwd V, dkv dO)  144 el =  72 dw = 8 x 9
+// ---------------------------------------------------------------------------
+
+constexpr int MLA_TR_KROW2 = MLA_PF_QK + 16;  // a 192-wide tile read both ways
+// 16-row sub-tiles per wave: forward as the prefill kernel; dq holds Q (24), dO
+// (16) and the fp32 dQ (48 registers) per sub-tile, and two of them spill
+// (resource table in docs/KERNELS.md)
+constexpr int MLA_TR_FWD_NT = 2, MLA_TR_DQ_NT = 1;
+
+// A 32-position tile of k_nope, v and the rope key, 1280 16-byte pieces, 5 per
+// thread, positions clamped to `last` (attn_prefill_mla_kernel's staging):
+//   k_nope, v 512 each: piece e = tid + 256 i -> position e >> 4, dims (e & 15) * 8
+//   rope      256:      position tid >> 3, dims (tid & 7) * 8
+struct MlaTrTile { ushort8 k[2], v[2], r; };
+
+DEVINL void mla_tr_tile_load(MlaTrTile& s, const unsigned short* __restrict__ kvb, long long kv_s,
+                             const unsigned short* __restrict__ rotb, long long rot_s, int p0, int last, int tid) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int e = tid + i * 256;
+    const size_t prow = (size_t)min(p0 + (e >> 4), last) * kv_s;
+    s.k[i] = *(const ushort8*)(kvb + prow + (e & 15) * 8);
+    s.v[i] = *(const ushort8*)(kvb + prow + MLA_PF_NOPE + (e & 15) * 8);
+  }
+  s.r = *(const ushort8*)(rotb + (size_t)min(p0 + (tid >> 3), last) * rot_s + (tid & 7) * 8);
+}
+
+template <int KROW, int VROW>
+DEVINL void mla_tr_tile_store(const MlaTrTile& s, unsigned short* dk, unsigned short* dv, int tid) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int e = tid + i * 256;
+    *(ushort8*)(dk + (e >> 4) * KROW + (e & 15) * 8) = s.k[i];
+    *(ushort8*)(dv + (e >> 4) * VROW + (e & 15) * 8) = s.v[i];
+  }
+  *(ushort8*)(dk + (tid >> 3) * KROW + MLA_PF_NOPE + (tid & 7) * 8) = s.r;
+}
+
+// Forward. Grid: one 4-wave workgroup per (q block, b, h), heads fastest (the
+// rope tile of a (q block, b) stays in L2), late q blocks first. Rows at or
+// beyond S are clamped on load and never stored; clamped positions are beyond
+// every real row's causal limit and masked before the maximum.
+template <int NT>
+__global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_train_mla_fwd_kernel(
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ kvx,
+    const unsigned short* __restrict__ rot, unsigned short* __restrict__ out, float* __restrict__ lse,
+    int B, int S, int H, AtStrides qs, AtStrides ks, long long rot_b, long long rot_s, float scale) {
+  constexpr int NC = MLA_PF_QK / 32, NG = MLA_PF_V / 16;
+  constexpr int QROWS = 64 * NT;
+  constexpr int KROW = MLA_PF_KROW, VROW = MLA_PF_VROW;
+  const int qblocks = (S + QROWS - 1) / QROWS;
+  const int h = blockIdx.x % H;
+  const int t1 = blockIdx.x / H;
+  const int b = t1 % B;
+  const int qb = qblocks - 1 - t1 / B;
+  const int tid = threadIdx.x;
+  const int wv = tid >> 6;
+  const int lane = tid & 63;
+  const int col = lane & 15, quad = lane >> 4;
+
+  __shared__ __attribute__((aligned(16))) unsigned short kv_lds[2][32 * KROW + 32 * VROW];
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][16 * 48 * NT];
+
+  const int r0 = qb * QROWS + wv * (16 * NT);
+  bf16x8 qf[NT][NC];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int row = min(r0 + t * 16 + col, S - 1);
+    const unsigned short* qrow = q + (size_t)b * qs.b + (size_t)row * qs.s + (size_t)h * qs.h;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) qf[t][c] = frag_load<false>(qrow + c * 32 + quad * 8);
+  }
+
+  float m[NT][4], lsum[NT][4];
+  floatx4 acco[NT][NG];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[t][r] = -INFINITY; lsum[t][r] = 0.f; }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int g = 0; g < NG; ++g) acco[t][g] = (floatx4)(0.f);
+
+  // causal end of the block: positions [0, kv_end), kv_end <= S
+  const int kv_end = min(qb * QROWS + QROWS, S);
+  const int ntiles = (kv_end + 31) >> 5;
+
+  const unsigned short* kvb = kvx + (size_t)b * ks.b + (size_t)h * ks.h;
+  const unsigned short* rotb = rot + (size_t)b * rot_b;
+  MlaTrTile st;
+  mla_tr_tile_load(st, kvb, ks.s, rotb, rot_s, 0, S - 1, tid);
+  mla_tr_tile_store<KROW, VROW>(st, kv_lds[0], kv_lds[0] + 32 * KROW, tid);
+  mla_pf_barrier();
+
+  unsigned short* plds = plds_all[wv];
+  for (int tp = 0; tp < ntiles; ++tp) {
+    const int buf = tp & 1;
+    const bool more = tp + 1 < ntiles;
+    if (more) mla_tr_tile_load(st, kvb, ks.s, rotb, rot_s, (tp + 1) * 32, S - 1, tid);  // under this tile's MFMAs
+    const unsigned short* dk = kv_lds[buf];
+    const unsigned short* dv = kv_lds[buf] + 32 * KROW;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      // wave-uniform: a tile wholly above the sub-tile's last row is all masked.
+      // Tile 0 is never skipped and every row sees position 0, so m is finite
+      // from the first tile on.
+      if (tp * 32 > r0 + t * 16 + 15) continue;
+      floatx4 sc[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        sc[hh] = (floatx4)(0.f);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const bf16x8 kf = *reinterpret_cast<const bf16x8*>(dk + (hh * 16 + col) * KROW + c * 32 + quad * 8);
+          sc[hh] = Frag<false>::mfma(qf[t][c], kf, sc[hh]);
+        }
+      }
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int pos = tp * 32 + hh * 16 + col;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = r0 + t * 16 + quad * 4 + r;
+          sc[hh][r] = (pos <= row) ? sc[hh][r] * scale : -INFINITY;
+        }
+      }
+      float rmax[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(sc[0][r], sc[1][r]);
+#pragma unroll
+      for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rmax[r] = fmaxf(rmax[r], mla_pf_lane_xor(rmax[r], lane, mm));
+      float alpha[4], rsum[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float mn = fmaxf(m[t][r], rmax[r]);
+        alpha[r] = (lsum[t][r] > 0.f) ? __expf(m[t][r] - mn) : 0.f;
+        m[t][r] = mn;
+        const float p0 = __expf(sc[0][r] - mn);
+        const float p1 = __expf(sc[1][r] - mn);
+        sc[0][r] = p0;
+        sc[1][r] = p1;
+        rsum[r] = p0 + p1;
+      }
+#pragma unroll
+      for (int mm = 1; mm < 16; mm <<= 1)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rsum[r] += mla_pf_lane_xor(rsum[r], lane, mm);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) lsum[t][r] = lsum[t][r] * alpha[r] + rsum[r];
+      attn_rescale(acco[t], alpha, 1.f);
+      unsigned short* pl = plds + t * 16 * 48;
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          pl[(quad * 4 + r) * 48 + hh * 16 + col] = f2b(sc[hh][r]);
+      const bf16x8 pf = at_image_frag(pl, lane);
+#pragma unroll
+      for (int g = 0; g < NG; ++g)
+        acco[t][g] = Frag<false>::mfma(pf, at_tr_frag(dv + g * 16, VROW, lane), acco[t][g]);
+    }
+    if (more) mla_tr_tile_store<KROW, VROW>(st, kv_lds[buf ^ 1], kv_lds[buf ^ 1] + 32 * KROW, tid);
+    mla_pf_barrier();
+  }
+
+  // out[b, row, h, :] = acc / l (contiguous), lse[b, h, row] = m + log(l)
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = r0 + t * 16 + quad * 4 + r;
+      if (row < S) {
+        const float inv = 1.f / lsum[t][r];
+        unsigned short* orow = out + (((size_t)b * S + row) * H + h) * MLA_PF_V;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) orow[g * 16 + col] = f2b(acco[t][g][r] * inv);
+        if (col == 0) lse[((size_t)b * H + h) * S + row] = m[t][r] + __logf(lsum[t][r]);
+      }
+    }
+  }
+}
+
+// Backward, dQ. The forward's grid at 64 * NT rows per block; a wave holds its
+// rows' Q (192) and dO (128) fragments, their lse and delta[r] = sum_d dO out
+// (fp32, from the wave's own rows, written to delta [B, H, S] for the dkv
+// kernel). Per tile P = exp(scale S - lse), dP = dO V^T over 128 dims,
+// dS = P (dP - delta) rounded once to bf16 through the wave's image, and
+// dQ += dS K over all 192 dims: the staged K tile (nope from kvx, rope from
+// rot) is read by b128 for the scores and by the transposing read here, V by
+// b128 only. Writes scale * dQ; dout / out [B, S, H, 128] and dq [B, S, H, 192]
+// are contiguous.
+template <int NT>
+__global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_train_mla_bwd_dq_kernel(
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ kvx,
+    const unsigned short* __restrict__ rot, const unsigned short* __restrict__ out,
+    const unsigned short* __restrict__ dout, const float* __restrict__ lse, float* __restrict__ delta,
+    unsigned short* __restrict__ dq, int B, int S, int H, AtStrides qs, AtStrides ks,
+    long long rot_b, long long rot_s, float scale) {
+  constexpr int NCK = MLA_PF_QK / 32, NCV = MLA_PF_V / 32, NG = MLA_PF_QK / 16;
+  constexpr int QROWS = 64 * NT;
+  constexpr int KROW = MLA_TR_KROW2, VROW = AT_BROW(MLA_PF_V);
+  const int qblocks = (S + QROWS - 1) / QROWS;
+  const int h = blockIdx.x % H;
+  const int t1 = blockIdx.x / H;
+  const int b = t1 % B;
+  const int qb = qblocks - 1 - t1 / B;
+  const int tid = threadIdx.x;
+  const int wv = tid >> 6;
+  const int lane = tid & 63;
+  const int col = lane & 15, quad = lane >> 4;
+
+  __shared__ __attribute__((aligned(16))) unsigned short kv_lds[2][32 * KROW + 32 * VROW];
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][16 * 48 * NT];
+
+  const int r0 = qb * QROWS + wv * (16 * NT);
+  const size_t bh = (size_t)b * H + h;
+  bf16x8 qf[NT][NCK], dof[NT][NCV];
+  float ls[NT][4], dl[NT][4];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int row = min(r0 + t * 16 + col, S - 1);
+    const unsigned short* qrow = q + (size_t)b * qs.b + (size_t)row * qs.s + (size_t)h * qs.h;
+    const size_t orow = (((size_t)b * S + row) * H + h) * MLA_PF_V;
+#pragma unroll
+    for (int c = 0; c < NCK; ++c) qf[t][c] = frag_load<false>(qrow + c * 32 + quad * 8);
+    float d = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCV; ++c) {
+      dof[t][c] = frag_load<false>(dout + orow + c * 32 + quad * 8);
+      const bf16x8 of = frag_load<false>(out + orow + c * 32 + quad * 8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) d += (float)dof[t][c][j] * (float)of[j];
+    }
+    d += mla_pf_lane_xor(d, lane, 16);
+    d += mla_pf_lane_xor(d, lane, 32);  // every lane: delta of row `col`
+    if (quad == 0 && r0 + t * 16 + col < S) delta[bh * S + row] = d;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      dl[t][r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((quad * 4 + r) << 2, __builtin_bit_cast(int, d)));
+      ls[t][r] = lse[bh * S + min(r0 + t * 16 + quad * 4 + r, S - 1)];
+    }
+  }
+
+  floatx4 acc[NT][NG];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int g = 0; g < NG; ++g) acc[t][g] = (floatx4)(0.f);
+
+  const int kv_end = min(qb * QROWS + QROWS, S);
+  const int ntiles = (kv_end + 31) >> 5;
+  const unsigned short* kvb = kvx + (size_t)b * ks.b + (size_t)h * ks.h;
+  const unsigned short* rotb = rot + (size_t)b * rot_b;
+  MlaTrTile st;
+  mla_tr_tile_load(st, kvb, ks.s, rotb, rot_s, 0, S - 1, tid);
+  mla_tr_tile_store<KROW, VROW>(st, kv_lds[0], kv_lds[0] + 32 * KROW, tid);
+  mla_pf_barrier();
+
+  unsigned short* plds = plds_all[wv];
+  for (int tp = 0; tp < ntiles; ++tp) {
+    const int buf = tp & 1;
+    const bool more = tp + 1 < ntiles;
+    if (more) mla_tr_tile_load(st, kvb, ks.s, rotb, rot_s, (tp + 1) * 32, S - 1, tid);
+    const unsigned short* dk = kv_lds[buf];
+    const unsigned short* dv = kv_lds[buf] + 32 * KROW;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      if (tp * 32 > r0 + t * 16 + 15) continue;  // wave-uniform: all masked, dS = 0
+      floatx4 sc[2], dp[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        sc[hh] = (floatx4)(0.f);
+        dp[hh] = (floatx4)(0.f);
+#pragma unroll
+        for (int c = 0; c < NCK; ++c) {
+          const bf16x8 kf = *reinterpret_cast<const bf16x8*>(dk + (hh * 16 + col) * KROW + c * 32 + quad * 8);
+          sc[hh] = Frag<false>::mfma(qf[t][c], kf, sc[hh]);
+        }
+#pragma unroll
+        for (int c = 0; c < NCV; ++c) {
+          const bf16x8 vf = *reinterpret_cast<const bf16x8*>(dv + (hh * 16 + col) * VROW + c * 32 + quad * 8);
+          dp[hh] = Frag<false>::mfma(dof[t][c], vf, dp[hh]);
+        }
+      }
+      unsigned short* pl = plds + t * 16 * 48;
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int pos = tp * 32 + hh * 16 + col;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = r0 + t * 16 + quad * 4 + r;
+          const float p = (pos <= row) ? __expf(sc[hh][r] * scale - ls[t][r]) : 0.f;
+          pl[(quad * 4 + r) * 48 + hh * 16 + col] = f2b(p * (dp[hh][r] - dl[t][r]));
+        }
+      }
+      const bf16x8 dsf = at_image_frag(pl, lane);
+#pragma unroll
+      for (int g = 0; g < NG; ++g)
+        acc[t][g] = Frag<false>::mfma(dsf, at_tr_frag(dk + g * 16, KROW, lane), acc[t][g]);
+    }
+    if (more) mla_tr_tile_store<KROW, VROW>(st, kv_lds[buf ^ 1], kv_lds[buf ^ 1] + 32 * KROW, tid);
+    mla_pf_barrier();
+  }
+
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = r0 + t * 16 + quad * 4 + r;
+      if (row < S) {
+        unsigned short* drow = dq + (((size_t)b * S + row) * H + h) * MLA_PF_QK;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) drow[g * 16 + col] = f2b(acc[t][g][r] * scale);
+      }
+    }
+  }
+}
+
+// Backward, dK and dV. Grid: one 4-wave workgroup per (kv block of 64
+// positions, b, h), early kv blocks (the long ones) first; a wave owns 16
+// positions: their K (192: kvx | rot) and V (128) fragments and the fp32 dK
+// (48 registers per lane) and dV (32) accumulators stay in registers. One flat
+// double-buffered loop walks the 32-row q tiles from the block's first
+// position to S; a tile's Q (192) and dO (128) rows, lse and delta are staged
+// through LDS, both tiles read both ways. Per tile, i = position, j = q row:
+//   S^T = K Q^T, P^T = exp(scale S^T - lse[j]) where j >= i and j < S, else 0
+//   dV += P^T dO;  dP^T = V dO^T;  dS^T = P^T (dP^T - delta[j]);  dK += dS^T Q
+// Each row is written once: d_kvx[b, t, h, 0:128] = scale dK_nope and
+// d_kvx[b, t, h, 128:256] = dV in bf16, ws[b, h, t, 0:64] = scale dK_rope in fp32.
+__global__ __launch_bounds__(256, 2) MLA_PF_NO_PK_F32 void attn_train_mla_bwd_dkv_kernel(
+    const unsigned short* __restrict__ q, const unsigned short* __restrict__ kvx,
+    const unsigned short* __restrict__ rot, const unsigned short* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    unsigned short* __restrict__ d_kvx, float* __restrict__ ws, int B, int S, int H,
+    AtStrides qs, AtStrides ks, long long rot_b, long long rot_s, float scale) {
+  constexpr int NCK = MLA_PF_QK / 32, NCV = MLA_PF_V / 32, NGK = MLA_PF_QK / 16, NGV = MLA_PF_V / 16;
+  constexpr int QROW = MLA_TR_KROW2, OROW = AT_TROW(MLA_PF_V);
+  constexpr int QPIECES = MLA_PF_QK / 8;  // 16-byte pieces of a Q row
+  const int h = blockIdx.x % H;
+  const int t1 = blockIdx.x / H;
+  const int b = t1 % B;
+  const int kb = t1 / B;
+  const int tid = threadIdx.x;
+  const int wv = tid >> 6;
+  const int lane = tid & 63;
+  const int col = lane & 15, quad = lane >> 4;
+
+  __shared__ __attribute__((aligned(16))) unsigned short qd_lds[2][32 * QROW + 32 * OROW];  // Q tile, dO tile
+  __shared__ float ld_lds[2][64];                                                           // lse[32], delta[32]
+  __shared__ __attribute__((aligned(16))) unsigned short plds_all[4][2 * 16 * 48];          // P^T image, dS^T image
+
+  const int p0 = kb * 64 + wv * 16;
+  bf16x8 kf[NCK], vf[NCV];
+  {
+    const int pos = min(p0 + col, S - 1);  // positions >= S: every q row is masked for them, never stored
+    const unsigned short* krow = kvx + (size_t)b * ks.b + (size_t)pos * ks.s + (size_t)h * ks.h;
+    const unsigned short* rrow = rot + (size_t)b * rot_b + (size_t)pos * rot_s;
+#pragma unroll
+    for (int c = 0; c < MLA_PF_NOPE / 32; ++c) kf[c] = frag_load<false>(krow + c * 32 + quad * 8);
+#pragma unroll
+    for (int c = 0; c < MLA_ROPE / 32; ++c) kf[MLA_PF_NOPE / 32 + c] = frag_load<false>(rrow + c * 32 + quad * 8);
+#pragma unroll
+    for (int c = 0; c < NCV; ++c) vf[c] = frag_load<false>(krow + MLA_PF_NOPE + c * 32 + quad * 8);
+  }
+  floatx4 acck[NGK], accv[NGV];
+#pragma unroll
+  for (int g = 0; g < NGK; ++g) acck[g] = (floatx4)(0.f);
+#pragma unroll
+  for (int g = 0; g < NGV; ++g) accv[g] = (floatx4)(0.f);
+
+  const int tq0 = kb * 2;                 // the q tile holding the block's first position
+  const int ntq = ((S + 31) >> 5) - tq0;  // >= 1: kb * 64 < S
+  const unsigned short* qbase = q + (size_t)b * qs.b + (size_t)h * qs.h;
+  const unsigned short* dobase = dout + ((size_t)b * S * H + h) * MLA_PF_V;
+  const size_t bh = (size_t)b * H + h;
+  ushort8 sq[3], sdo[2];  // 32 x 24 and 32 x 16 pieces over 256 threads
+  float sld;
+  auto stage_load = [&](int it) __attribute__((always_inline)) {
+    const int row0 = (tq0 + it) * 32;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int e = tid + i * 256;
+      sq[i] = *(const ushort8*)(qbase + (size_t)min(row0 + e / QPIECES, S - 1) * qs.s + (e % QPIECES) * 8);
+    }
+    at_tile_load<MLA_PF_V>(sdo, dobase, (long long)H * MLA_PF_V, row0, S - 1, tid);
+    if (tid < 64) sld = (tid < 32 ? lse : delta)[bh * S + min(row0 + (tid & 31), S - 1)];
+  };
+  auto stage_store = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int e = tid + i * 256;
+      *(ushort8*)(qd_lds[buf] + (e / QPIECES) * QROW + (e % QPIECES) * 8) = sq[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int e = tid + i * 256;
+      *(ushort8*)(qd_lds[buf] + 32 * QROW + (e >> 4) * OROW + (e & 15) * 8) = sdo[i];
+    }
+    if (tid < 64) ld_lds[buf][tid] = sld;
+  };
+
+  stage_load(0);
+  stage_store(0);
+  mla_pf_barrier();
+
+  unsigned short* pl = plds_all[wv];
+  unsigned short* dsl = plds_all[wv] + 16 * 48;
+  for (int it = 0; it < ntq; ++it) {
+    const int buf = it & 1;
+    const bool more = it + 1 < ntq;
+    if (more) stage_load(it + 1);
+    const unsigned short* tq = qd_lds[buf];
+    const unsigned short* tdo = qd_lds[buf] + 32 * QROW;
+    const int row0 = (tq0 + it) * 32;
+    if (row0 + 31 >= p0) {  // wave-uniform: a tile wholly before the wave's positions is all masked
+      floatx4 sc[2], dp[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        sc[hh] = (floatx4)(0.f);
+        dp[hh] = (floatx4)(0.f);
+#pragma unroll
+        for (int c = 0; c < NCK; ++c) {
+          const bf16x8 qb = *reinterpret_cast<const bf16x8*>(tq + (hh * 16 + col) * QROW + c * 32 + quad * 8);
+          sc[hh] = Frag<false>::mfma(kf[c], qb, sc[hh]);
+        }
+#pragma unroll
+        for (int c = 0; c < NCV; ++c) {
+          const bf16x8 ob = *reinterpret_cast<const bf16x8*>(tdo + (hh * 16 + col) * OROW + c * 32 + quad * 8);
+          dp[hh] = Frag<false>::mfma(vf[c], ob, dp[hh]);
+        }
+      }
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int qrow = row0 + hh * 16 + col;
+        const float l = ld_lds[buf][hh * 16 + col];
+        const float de = ld_lds[buf][32 + hh * 16 + col];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int pos = p0 + quad * 4 + r;
+          const float p = (qrow >= pos && qrow < S) ? __expf(sc[hh][r] * scale - l) : 0.f;
+          pl[(quad * 4 + r) * 48 + hh * 16 + col] = f2b(p);
+          dsl[(quad * 4 + r) * 48 + hh * 16 + col] = f2b(p * (dp[hh][r] - de));
+        }
+      }
+      const bf16x8 pf = at_image_frag(pl, lane);
+      const bf16x8 dsf = at_image_frag(dsl, lane);
+#pragma unroll
+      for (int g = 0; g < NGV; ++g) accv[g] = Frag<false>::mfma(pf, at_tr_frag(tdo + g * 16, OROW, lane), accv[g]);
+#pragma unroll
+      for (int g = 0; g < NGK; ++g) acck[g] = Frag<false>::mfma(dsf, at_tr_frag(tq + g * 16, QROW, lane), acck[g]);
+    }
+    if (more) stage_store(buf ^ 1);
+    mla_pf_barrier();
+  }
+
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int pos = p0 + quad * 4 + r;
+    if (pos < S) {
+      unsigned short* o = d_kvx + (((size_t)b * S + pos) * H + h) * (MLA_PF_NOPE + MLA_PF_V);
+      float* w = ws + (bh * S + pos) * MLA_ROPE;
+#pragma unroll
+      for (int g = 0; g < MLA_PF_NOPE / 16; ++g) o[g * 16 + col] = f2b(acck[g][r] * scale);
+#pragma unroll
+      for (int g = 0; g < NGV; ++g) o[MLA_PF_NOPE + g * 16 + col] = f2b(accv[g][r]);
+#pragma unroll
+      for (int g = 0; g < MLA_ROPE / 16; ++g) w[g * 16 + col] = acck[MLA_PF_NOPE / 16 + g][r] * scale;
+    }
+  }
+}
+
+// d_rot[b, t, :] = sum over h of ws[b, h, t, :], heads in ascending order, fp32,
+// rounded once to bf16: the deterministic stand-in for an atomic add across
+// the heads' workgroups. One thread per 4 dims.
+__global__ __launch_bounds__(256) MLA_PF_NO_PK_F32 void attn_train_mla_rope_reduce_kernel(
+    const float* __restrict__ ws, unsigned short* __restrict__ d_rot, int B, int S, int H) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)B * S * (MLA_ROPE / 4)) return;
+  const int d4 = (int)(idx % (MLA_ROPE / 4));
+  const size_t t = (idx / (MLA_ROPE / 4)) % S;
+  const size_t b = idx / (MLA_ROPE / 4) / S;
+  float a[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int h = 0; h < H; ++h) {
+    const float4 x = *(const float4*)(ws + ((b * H + h) * S + t) * MLA_ROPE + d4 * 4);
+    a[0] += x.x; a[1] += x.y; a[2] += x.z; a[3] += x.w;
+  }
+  ushort4 o;
+  o.x = f2b(a[0]); o.y = f2b(a[1]); o.z = f2b(a[2]); o.w = f2b(a[3]);
+  *(ushort4*)(d_rot + idx * 4) = o;
+}
+
+// ---------------------------------------------------------------------------
 // fp8-KV flash prefill (HD = 128 or 256, causal, GQA): attn_prefill_mfma_kernel
 // over the e4m3 packed cache and its per-position scales sk / sv [B, KVH, T32].
 //
@@ -5638,6 +6154,84 @@ std::vector<torch::Tensor> attn_train_bwd(torch::Tensor dout, torch::Tensor q, t
   return {dq, dk, dv};
 }
 
+// MLA training attention. q: [B, S, H, 192] (nope | roped tail), kvx:
+// [B, S, H, 256] (the kv_b_proj output per head, k_nope | v), k_rot: [B, S, 64]
+// (the roped shared key) bf16, read in place: any strides in whole 16-byte
+// pieces, last dim contiguous.
+struct AttnTrainMlaShape {
+  int B, S, H;
+  AtStrides qs, ks;
+  long long rot_b, rot_s;
+};
+
+static AttnTrainMlaShape attn_train_mla_shape(const char* what, const torch::Tensor& q, const torch::Tensor& kvx,
+                                              const torch::Tensor& k_rot, double scale) {
+  for (const torch::Tensor* t : {&q, &kvx, &k_rot}) {
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kBFloat16, what, ": q, kvx, k_rot are bf16 GPU tensors");
+    TORCH_CHECK(t->stride(-1) == 1 && (uintptr_t)t->data_ptr() % 16 == 0, what, ": rows must be contiguous and 16-byte aligned");
+    for (int d = 0; d + 1 < t->dim(); ++d) TORCH_CHECK(t->stride(d) % 8 == 0, what, ": strides in whole 16-byte pieces");
+  }
+  TORCH_CHECK(q.dim() == 4 && kvx.dim() == 4 && k_rot.dim() == 3, what, ": q, kvx are 4-d and k_rot is 3-d");
+  TORCH_CHECK(q.size(3) == MLA_PF_QK && kvx.size(3) == MLA_PF_NOPE + MLA_PF_V && k_rot.size(2) == MLA_ROPE, what,
+              ": nope 128 / rope 64 / v 128 only, got q ", q.size(3), ", kvx ", kvx.size(3), ", k_rot ", k_rot.size(2));
+  AttnTrainMlaShape s{(int)q.size(0), (int)q.size(1), (int)q.size(2), {q.stride(0), q.stride(1), q.stride(2)},
+                      {kvx.stride(0), kvx.stride(1), kvx.stride(2)}, k_rot.stride(0), k_rot.stride(1)};
+  CHK(s.B > 0 && s.S > 0 && s.H > 0 && scale > 0.0);
+  CHK(kvx.size(0) == s.B && kvx.size(1) == s.S && kvx.size(2) == s.H && k_rot.size(0) == s.B && k_rot.size(1) == s.S);
+  CHK((int64_t)s.B * s.H * ((s.S + 63) / 64) <= INT_MAX);
+  return s;
+}
+
+// -> (out [B, S, H, 128] bf16, lse [B, H, S] fp32 in units of the scaled score)
+std::vector<torch::Tensor> attn_train_mla_fwd(torch::Tensor q, torch::Tensor kvx, torch::Tensor k_rot, double scale) {
+  const AttnTrainMlaShape s = attn_train_mla_shape("attn_train_mla_fwd", q, kvx, k_rot, scale);
+  auto out = torch::empty({s.B, s.S, s.H, MLA_PF_V}, q.options());
+  auto lse = torch::empty({s.B, s.H, s.S}, q.options().dtype(torch::kFloat32));
+  constexpr int QROWS = 64 * MLA_TR_FWD_NT;
+  const unsigned blocks = (unsigned)s.B * ((s.S + QROWS - 1) / QROWS) * s.H;
+  hipLaunchKernelGGL((attn_train_mla_fwd_kernel<MLA_TR_FWD_NT>), dim3(blocks), dim3(256), 0, cur_stream(),
+                     (const unsigned short*)q.data_ptr(), (const unsigned short*)kvx.data_ptr(),
+                     (const unsigned short*)k_rot.data_ptr(), (unsigned short*)out.data_ptr(),
+                     lse.data_ptr<float>(), s.B, s.S, s.H, s.qs, s.ks, s.rot_b, s.rot_s, (float)scale);
+  return {out, lse};
+}
+
+// dout / out: [B, S, H, 128] bf16 contiguous, lse: what attn_train_mla_fwd
+// returned -> (dq [B, S, H, 192], d_kvx [B, S, H, 256], d_k_rot [B, S, 64]) bf16
+// contiguous. Three launches on the current stream; the workspace is delta
+// [B, H, S] and the per-head rope-key gradient [B, H, S, 64], both fp32.
+std::vector<torch::Tensor> attn_train_mla_bwd(torch::Tensor dout, torch::Tensor q, torch::Tensor kvx,
+                                              torch::Tensor k_rot, torch::Tensor out, torch::Tensor lse, double scale) {
+  const AttnTrainMlaShape s = attn_train_mla_shape("attn_train_mla_bwd", q, kvx, k_rot, scale);
+  for (const torch::Tensor* t : {&dout, &out})
+    CHK(t->is_cuda() && t->dtype() == torch::kBFloat16 && t->is_contiguous() && t->dim() == 4 && t->size(0) == s.B &&
+        t->size(1) == s.S && t->size(2) == s.H && t->size(3) == MLA_PF_V && (uintptr_t)t->data_ptr() % 16 == 0);
+  CHK(lse.is_cuda() && lse.dtype() == torch::kFloat32 && lse.is_contiguous());
+  CHK(lse.dim() == 3 && lse.size(0) == s.B && lse.size(1) == s.H && lse.size(2) == s.S);
+  auto delta = torch::empty_like(lse);
+  auto ws = torch::empty({s.B, s.H, s.S, MLA_ROPE}, lse.options());
+  auto dq = torch::empty({s.B, s.S, s.H, MLA_PF_QK}, q.options());
+  auto d_kvx = torch::empty({s.B, s.S, s.H, MLA_PF_NOPE + MLA_PF_V}, q.options());
+  auto d_rot = torch::empty({s.B, s.S, MLA_ROPE}, q.options());
+  constexpr int QROWS = 64 * MLA_TR_DQ_NT;
+  const unsigned qblocks = (unsigned)s.B * ((s.S + QROWS - 1) / QROWS) * s.H;
+  hipLaunchKernelGGL((attn_train_mla_bwd_dq_kernel<MLA_TR_DQ_NT>), dim3(qblocks), dim3(256), 0, cur_stream(),
+                     (const unsigned short*)q.data_ptr(), (const unsigned short*)kvx.data_ptr(),
+                     (const unsigned short*)k_rot.data_ptr(), (const unsigned short*)out.data_ptr(),
+                     (const unsigned short*)dout.data_ptr(), lse.data_ptr<float>(), delta.data_ptr<float>(),
+                     (unsigned short*)dq.data_ptr(), s.B, s.S, s.H, s.qs, s.ks, s.rot_b, s.rot_s, (float)scale);
+  const unsigned kvblocks = (unsigned)s.B * ((s.S + 63) / 64) * s.H;
+  hipLaunchKernelGGL(attn_train_mla_bwd_dkv_kernel, dim3(kvblocks), dim3(256), 0, cur_stream(),
+                     (const unsigned short*)q.data_ptr(), (const unsigned short*)kvx.data_ptr(),
+                     (const unsigned short*)k_rot.data_ptr(), (const unsigned short*)dout.data_ptr(),
+                     lse.data_ptr<float>(), delta.data_ptr<float>(), (unsigned short*)d_kvx.data_ptr(),
+                     ws.data_ptr<float>(), s.B, s.S, s.H, s.qs, s.ks, s.rot_b, s.rot_s, (float)scale);
+  const int64_t quads = (int64_t)s.B * s.S * (MLA_ROPE / 4);
+  hipLaunchKernelGGL(attn_train_mla_rope_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0,
+                     cur_stream(), ws.data_ptr<float>(), (unsigned short*)d_rot.data_ptr(), s.B, s.S, s.H);
+  return {dq, d_kvx, d_rot};
+}
+
 torch::Tensor mfma16_probe(torch::Tensor a, torch::Tensor b) {
   CHK(a.is_cuda() && a.dtype() == torch::kBFloat16 && a.is_contiguous() && a.numel() == 16 * 32);
   CHK(b.is_cuda() && b.dtype() == torch::kBFloat16 && b.is_contiguous() && b.numel() == 32 * 16);
@@ -6248,6 +6842,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_train_bwd", &attn_train_bwd,
         "training attention backward, deterministic -> (dq, dk, dv) bf16 contiguous",
         py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("scale"));
+  m.def("attn_train_mla_fwd", &attn_train_mla_fwd,
+        "MLA training attention forward (causal, bf16, nope 128 | shared rope 64, v 128; q / kvx / k_rot strided "
+        "views) -> (out [B, S, H, 128], lse [B, H, S])",
+        py::arg("q"), py::arg("kvx"), py::arg("k_rot"), py::arg("scale"));
+  m.def("attn_train_mla_bwd", &attn_train_mla_bwd,
+        "MLA training attention backward, deterministic -> (dq, d_kvx = dk_nope | dv, d_k_rot) bf16 contiguous",
+        py::arg("dout"), py::arg("q"), py::arg("kvx"), py::arg("k_rot"), py::arg("out"), py::arg("lse"),
+        py::arg("scale"));
   m.def("attn_prefill_mla", &attn_prefill_mla,
         "MLA causal flash prefill (qk 192 = nope 128 | shared rope 64, v 128) on matrix cores, "
         "K/V read in place from the kv_b_proj output and the plain rope cache",

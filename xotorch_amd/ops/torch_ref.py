@@ -206,6 +206,25 @@ def attn_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optiona
   return out.transpose(1, 2)
 
 
+def attn_train_mla(q: torch.Tensor, kvx: torch.Tensor, k_rot: torch.Tensor, scale: float) -> torch.Tensor:
+  """Cache-free causal MLA attention, differentiable (training / eval), the
+  definition of ops.attn_train_mla: q [B, S, H, nope + rope] (nope | roped
+  tail), kvx [B, S, H, nope + vd] (the kv_b_proj output per head, k_nope | v),
+  k_rot [B, S, rope] (the roped key shared by all heads) -> [B, S, H, vd].
+  nope is q's width less k_rot's. The explicit fp32 expression: the
+  rope key expanded over the heads, masked softmax, fp32 sums (no sdpa: its
+  ROCm flash backend refuses head dim 192)."""
+  B, S, H, _ = q.shape
+  nope = q.shape[3] - k_rot.shape[2]
+  wide = torch.promote_types(q.dtype, torch.float32)  # fp32 for bf16 / fp16 / fp32; an fp64 call stays fp64
+  k = torch.cat([kvx[..., :nope].to(wide), k_rot[:, :, None, :].expand(B, S, H, -1).to(wide)], dim=-1)
+  scores = torch.einsum("bshd,bthd->bhst", q.to(wide), k) * scale
+  pos = torch.arange(S, device=q.device)
+  scores = scores.masked_fill((pos[None, :] > pos[:, None])[None, None], float("-inf"))
+  out = torch.einsum("bhst,bthd->bshd", torch.softmax(scores, dim=-1), kvx[..., nope:].to(wide))
+  return out.to(q.dtype)
+
+
 def attn_decode(
   q: torch.Tensor,
   k_cache: torch.Tensor,
